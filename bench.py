@@ -11,12 +11,24 @@ K-1-sample halo with the left neighbour over RCCL (torch.distributed send/recv),
 halo-free interior of the chunk at once and the K-1 edge outputs once the halo has arrived --
 the only exchange the path needs, off the step's critical path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--workload fft|sos|resample` runs BASELINE.json configs[2..4] under the same contract (same
 JSON line, same sharding rules of SURVEY.md 8e); the default `fir` is configs[1], the
 configuration the metric is quoted on.
+
+A plain run does only what the headline needs: set-up, the untimed pre-warm and W warm-up steps,
+the K timed steps, and the JSON line (metric, value, unit, ms_per_step, ...).  `--full` adds what
+takes runs of its own: the roofline block (the K steps replayed with HIP events around every
+launch, HBM traffic of the committed PMC summary), the direct-kernel line of the FIR and the CPU
+baseline on the oracle (`--no-cpu` skips that one).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as float32 .npy
+files (complex data as [..., 2] = re, im): DIR/<name>_head.npy holds the first DUMP_HEAD elements,
+DIR/<name>.npy the whole output or, above its share of DUMP_BYTES, one element per block of
+2^k at an offset drawn from a fixed seed.  The inputs come from fixed seeds too, so two builds
+compare output for output.  With N ranks every rank writes its own files (rank<r>_<name>...).
 """
 import argparse
 import json
@@ -32,6 +44,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 LOG2N = 26
 K_TAPS = 127
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_HEAD = 16384              # leading elements of every output, written whole (stream / block boundaries)
 # HBM bytes per step: read at run time from the newest committed profiles/r*_pmc_traffic.txt (rocprofv3 --pmc
 # FETCH_SIZE / WRITE_SIZE in separate passes, scripts/profile_round.sh; mean KB per launch of each kernel).
 # gfx950 correction of MI355X_MICROARCH.md (HBM section): FETCH_SIZE counts 64 B per 128-B request on wide
@@ -155,6 +169,9 @@ class FirWorkload:
             self.pipe = sharding.HaloPipe(self.halo_in, self.rank, self.world, ring=self.ring, complex_view=True)
         self.ov.step(self.x, self.y, lambda: self.pipe.post(self.halo_out), first=(self.rank == 0 and not self.ring), consumed=self.pipe.consumed)
 
+    def outputs(self):
+        return {"y": self.y}
+
     def cpu_baseline(self):
         from oracle import pyoracle as orc
         rng = np.random.default_rng(2)
@@ -204,6 +221,9 @@ class FftWorkload:
 
     def step(self):
         self.p.step(self.x, True, self.y)
+
+    def outputs(self):
+        return {"y": self.y}
 
     def cpu_baseline(self):
         from oracle import pyoracle as orc
@@ -258,6 +278,9 @@ class SosWorkload:
             self.pipe = sharding.HaloPipe(self.halo_in, self.rank, self.world, ring=self.ring)
         self.ov.step(self.x, self.y, lambda: self.pipe.post(self.halo_out), first=(self.rank == 0 and not self.ring), consumed=self.pipe.consumed)
 
+    def outputs(self):
+        return {"y": self.y}
+
     def cpu_baseline(self):
         from oracle import pyoracle as orc
         z, p, mn, md = orc.design_butter_lp(12, 0.25)     # design_riia(12,"lp","butt",0.25)
@@ -293,6 +316,7 @@ class ResampleWorkload:
         self.halo_in_c = torch.zeros(14, dtype=self.x.dtype, device=dev)
         self.halo_in = torch.view_as_real(self.halo_in_c)
         self.pipe = None
+        self.last = None                          # what the last step returned: the outputs it produced (a view of y)
         self.units = float(self.n)
         self.alg_bytes = 8.0 * self.n + 8.0 * self.nout
         self.metric = "Msamples/s (input), 160/147 resampling of a cfloat stream, %d inputs per GPU" % self.n if args.scaling == "strong" \
@@ -307,12 +331,16 @@ class ResampleWorkload:
         if not self.dist:
             # every step resamples the same 2^27-sample shard from stream position `pos`
             self.r.seek(self.pos, None)
-            self.r.step(self.x, self.y)
+            self.last = self.r.step(self.x, self.y)
             return
         from libtsd_amd import sharding
         if self.pipe is None:
             self.pipe = sharding.HaloPipe(self.halo_in, self.rank, self.world, ring=self.ring, complex_view=True)
-        self.ov.step(self.x, self.y, self.pos, lambda: self.pipe.post(self.halo_out), first=(self.rank == 0 and not self.ring), consumed=self.pipe.consumed)
+        self.last = self.ov.step(self.x, self.y, self.pos, lambda: self.pipe.post(self.halo_out), first=(self.rank == 0 and not self.ring),
+                                 consumed=self.pipe.consumed)
+
+    def outputs(self):
+        return {"y": self.last}
 
     def cpu_baseline(self):
         from oracle import pyoracle as orc
@@ -340,6 +368,36 @@ def _size_note(kind, total, world, args):
     return "2^%d-sample %s per GPU" % (total.bit_length() - 1, kind)
 
 
+def _snapshot(outs, budget, torch):
+    """--dump-outputs, right after the timed region: device copies of the K-th step's outputs (or of their seeded sample),
+    so that the steps run after it (--full) cannot overwrite them; `budget` bytes in all.  -> {file name: tensor}"""
+    snap = {}
+    for name, y in outs.items():
+        v = torch.view_as_real(y).reshape(-1, 2) if y.is_complex() else y.reshape(-1)
+        snap[name + "_head"] = v[:DUMP_HEAD].clone()
+        row = 4 * (2 if v.dim() == 2 else 1)                                # float32 bytes per element in the file
+        share = budget // len(outs) - DUMP_HEAD * row - 2 * 4096            # (the head and the two .npy headers)
+        n = v.shape[0]
+        stride = 1
+        while n * row > stride * share:
+            stride *= 2
+        if stride == 1:
+            snap[name] = v.clone()
+            continue
+        # one element per block of `stride`, at an offset of a fixed seed: the same positions for the same shape on every run
+        blocks = n // stride
+        off = np.random.default_rng(20261016).integers(0, stride, blocks)
+        idx = torch.from_numpy(np.arange(blocks, dtype=np.int64) * stride + off).to(v.device)
+        snap[name] = v.index_select(0, idx)
+    return snap
+
+
+def _write_outputs(snap, dirname, prefix):
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in snap.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), v.float().cpu().numpy())
+
+
 def _self_launch(args):
     """`python3 bench.py --gpus N` started WITHOUT a launcher (WORLD_SIZE unset): start the N ranks as CHILD processes
     through torch.distributed.run, relay rank 0's JSON line and return the launcher's exit code.  Called before this
@@ -349,8 +407,11 @@ def _self_launch(args):
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
+    argv = sys.argv[1:]
+    if args.dump_outputs:
+        argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]      # (the ranks run from ROOT; the last one given counts)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: what RCCL needs on these hosts
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -363,6 +424,51 @@ def _self_launch(args):
     return p.wait()
 
 
+def _full_legs(args, t, torch, dev, rank, world, w, dt, run, kernel_ms, pre_warm, out):
+    """--full: the roofline block (kernel time of K replayed steps), the FIR's direct-kernel line and the CPU baseline, added to
+    rank 0's record `out`.  Every rank replays the same steps (the halo exchanges pair up)."""
+    kern_ms = kernel_ms(w, args.steps)
+    # two clocks, both reported under their own names: HIP events around the operator on its stream
+    # (the kernel's launch duration: `achieved` / `frac`, what the roofline is about) and the wall clock
+    # of the K timed steps (`value`, `ms_per_step`; `achieved_wall` / `frac_wall`: launch gaps included)
+    timer_note = ("achieved/frac: HIP events around every launch on the operator's stream (the K steps replayed right after the timed region); "
+                  "achieved_wall/frac_wall: the wall clock of the timed region, the denominator of `value`")
+    if getattr(w, "dist", False):
+        # a multi-rank step spans three streams (interior, exchange, edge) and is pipelined across steps: an event pair around it on
+        # one stream serialises it and adds two release fences -- the per-step figure is the wall clock's there
+        kern_ms = dt / args.steps * 1e3
+        timer_note = ("multi-rank step (interior / exchange / edge on their own streams, pipelined): achieved/frac and achieved_wall/frac_wall "
+                      "are both the wall clock of the timed region")
+    achieved = w.alg_bytes / (kern_ms * 1e-3) / 1e9
+    achieved_wall = w.alg_bytes * args.steps / dt / 1e9
+    traffic, traffic_src = pmc_traffic(args.workload) if w.traffic_ok else (None, None)
+    if rank == 0:
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4),
+                           "traffic": traffic, "traffic_source": traffic_src,
+                           "timer": timer_note,
+                           "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": w.alg_bytes,
+                           "achieved_wall": round(achieved_wall, 1), "frac_wall": round(achieved_wall / HBM_PEAK_GBS, 4)}
+    if world == 1:
+        if args.workload == "fir":
+            # secondary line: the direct kernel on the same data (rank-local, N=1 only)
+            # (same pre-warm and at least 20 timed steps: measured cold on 5 steps the line moved 25 % with --steps)
+            args_d = argparse.Namespace(**dict(vars(args), force_dist=False))
+            wd = FirWorkload(t, torch, dev, rank, world, args_d, method=t.FIR_DIRECT)
+            sd = max(20, args.steps // 4)
+            for _ in range(pre_warm // 2):
+                wd.step()
+            torch.cuda.synchronize()
+            dt_d = run(wd, sd, 5)
+            kern_d = kernel_ms(wd, sd)
+            out["direct"] = {"value": round(wd.units * sd / dt_d / 1e6, 1), "unit": "Msamples/s",
+                             "kernel_ms": round(kern_d, 4),
+                             "hbm_frac": round(wd.alg_bytes / (kern_d * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             "valu_frac_of_157.3TF": round(4.0 * K_TAPS * wd.n / (kern_d * 1e-3) / 157.3e12, 4)}
+        if not args.no_cpu:
+            out["cpu_baseline"] = w.cpu_baseline()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -370,7 +476,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="fir")
     ap.add_argument("--log2n", type=int, default=LOG2N, help="fir/sos: samples per GPU = 2^log2n (default: the BASELINE size)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the roofline block (K steps replayed with HIP events), the direct-kernel "
+                         "line of the FIR and the CPU baseline on the oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as float32 .npy files under DIR (at most 64 MB, seeded sample of larger outputs)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default): the per-GPU size is fixed; strong: the TOTAL is fixed and split over the ranks "
                          "(resample: the 2^30 inputs of configs[4]; fir/sos: 2^log2n samples; fft: the 256 transforms)")
@@ -446,10 +557,9 @@ def main():
             dist.barrier()
 
     def run(wl, steps, warmup):
-        """-> (wall seconds of the K timed steps, max over ranks; mean kernel ms of the same K steps replayed
-        with one HIP-event pair per launch).  The timed region carries no per-step events: each record is a
-        barrier packet between two launches (measured: ~6 us per step on the 0.22 ms FIR step), which belongs
-        to the measurement, not to the path."""
+        """-> wall seconds of the K timed steps, max over ranks.  The timed region carries no per-step events: each
+        record is a barrier packet between two launches (measured: ~6 us per step on the 0.22 ms FIR step), which
+        belongs to the measurement, not to the path."""
         for _ in range(warmup):
             wl.step()
         barrier()
@@ -460,8 +570,10 @@ def main():
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
-        dt = sharding.max_over_ranks(dt, dev, world, force=in_dist)
-        # kernel duration: the same steps again, every launch bracketed by events on its stream
+        return sharding.max_over_ranks(dt, dev, world, force=in_dist)
+
+    def kernel_ms(wl, steps):
+        """-> mean kernel ms of K more steps, replayed right after run() with one HIP-event pair per launch"""
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
         for i in range(steps):
             evs[i][0].record()
@@ -469,8 +581,7 @@ def main():
             evs[i][1].record()
         torch.cuda.synchronize()
         barrier()
-        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-        return dt, kern_ms
+        return float(np.mean([a.elapsed_time(b) for a, b in evs]))
 
     # GPU clock ramp: the first ~20 ms of kernels after an idle period run at a lower clock
     # (measured: 0.27 ms vs 0.22 ms per FIR step).  A fixed untimed pre-run brings the device to
@@ -480,22 +591,9 @@ def main():
     for _ in range(PRE_WARM):
         w.step()           # (every rank runs the same count: the halo exchanges pair up)
     torch.cuda.synchronize()
-    dt, kern_ms = run(w, args.steps, args.warmup)
+    dt = run(w, args.steps, args.warmup)
+    snap = _snapshot(w.outputs(), DUMP_BYTES // world, torch) if args.dump_outputs else None
     value = w.units * world * args.steps / dt / 1e6
-    # two clocks, both reported under their own names: HIP events around the operator on its stream
-    # (the kernel's launch duration: `achieved` / `frac`, what the roofline is about) and the wall clock
-    # of the K timed steps (`value`, `ms_per_step`; `achieved_wall` / `frac_wall`: launch gaps included)
-    timer_note = ("achieved/frac: HIP events around every launch on the operator's stream (the K steps replayed right after the timed region); "
-                  "achieved_wall/frac_wall: the wall clock of the timed region, the denominator of `value`")
-    if getattr(w, "dist", False):
-        # a multi-rank step spans three streams (interior, exchange, edge) and is pipelined across steps: an event pair around it on
-        # one stream serialises it and adds two release fences -- the per-step figure is the wall clock's there
-        kern_ms = dt / args.steps * 1e3
-        timer_note = ("multi-rank step (interior / exchange / edge on their own streams, pipelined): achieved/frac and achieved_wall/frac_wall "
-                      "are both the wall clock of the timed region")
-    achieved = w.alg_bytes / (kern_ms * 1e-3) / 1e9
-    achieved_wall = w.alg_bytes * args.steps / dt / 1e9
-    traffic, traffic_src = pmc_traffic(args.workload) if w.traffic_ok else (None, None)
 
     out = None
     if rank == 0:
@@ -511,30 +609,11 @@ def main():
             "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": w.dtype, "data": "synthetic", "config": cfg,
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "timer": timer_note,
-                         "kernel_ms": round(kern_ms, 4), "algorithmic_bytes_per_launch": w.alg_bytes,
-                         "achieved_wall": round(achieved_wall, 1), "frac_wall": round(achieved_wall / HBM_PEAK_GBS, 4)},
         }
-    if world == 1:
-        if args.workload == "fir":
-            # secondary line: the direct kernel on the same data (rank-local, N=1 only)
-            # (same pre-warm and at least 20 timed steps: measured cold on 5 steps the line moved 25 % with --steps)
-            args_d = argparse.Namespace(**dict(vars(args), force_dist=False))
-            wd = FirWorkload(t, torch, dev, rank, world, args_d, method=t.FIR_DIRECT)
-            sd = max(20, args.steps // 4)
-            for _ in range(PRE_WARM // 2):
-                wd.step()
-            torch.cuda.synchronize()
-            dt_d, kern_d = run(wd, sd, 5)
-            out["direct"] = {"value": round(wd.units * sd / dt_d / 1e6, 1), "unit": "Msamples/s",
-                             "kernel_ms": round(kern_d, 4),
-                             "hbm_frac": round(wd.alg_bytes / (kern_d * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                             "valu_frac_of_157.3TF": round(4.0 * K_TAPS * wd.n / (kern_d * 1e-3) / 157.3e12, 4)}
-        if not args.no_cpu:
-            out["cpu_baseline"] = w.cpu_baseline()
+    if args.full:
+        _full_legs(args, t, torch, dev, rank, world, w, dt, run, kernel_ms, PRE_WARM, out)
+    if snap is not None:
+        _write_outputs(snap, args.dump_outputs, "rank%d_" % rank if world > 1 else "")
     if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

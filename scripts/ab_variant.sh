@@ -5,6 +5,6 @@ v=$1; shift
 for i in 1 2 3; do
   for w in base $v; do
     if [ "$w" == base ]; then unset TSDGPU_LIB; else export TSDGPU_LIB=libtsd_amd/lib/variants/libtsdgpu_$w.so; fi
-    python bench.py --steps 200 --warmup 50 --no-cpu "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$w', d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'])"
+    python bench.py --full --steps 200 --warmup 50 --no-cpu "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$w', d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac'])"
   done
 done

@@ -15,9 +15,9 @@ for w in fir fft sos resample; do
   steps=$(steps_of $w)
   out=$ROOT/gpurun_out/${TAG}_prof_$w
   rm -rf $out
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python3 $ROOT/bench.py --workload $w --steps $steps --warmup 20 --no-cpu > $out.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python3 $ROOT/bench.py --full --workload $w --steps $steps --warmup 20 --no-cpu > $out.log 2>&1)
   cp $out/run_kernel_stats.csv gpurun_out/${TAG}_${w}_kernel_stats.csv
-  PMC_TRAFFIC_ONLY=1 scripts/pmc_collect.sh ${TAG}_$w bench.py --workload $w --steps 6 --warmup 2 --no-cpu > /dev/null 2>&1 || true
+  PMC_TRAFFIC_ONLY=1 scripts/pmc_collect.sh ${TAG}_$w bench.py --full --workload $w --steps 6 --warmup 2 --no-cpu > /dev/null 2>&1 || true
   echo "== $w profiled"
 done
 cat gpurun_out/pmc_${TAG}_*_summary.txt | grep -v "at::native\|rocclr\|hist_update" > gpurun_out/${TAG}_pmc_traffic.txt || true
@@ -25,7 +25,8 @@ cp gpurun_out/${TAG}_pmc_traffic.txt profiles/${TAG}_pmc_traffic.txt
 cat gpurun_out/${TAG}_pmc_traffic.txt
 for w in fir fft sos resample; do
   steps=$(steps_of $w)
-  python3 bench.py --workload $w --steps $steps --warmup 20 > gpurun_out/${TAG}_bench_$w.json 2> gpurun_out/${TAG}_bench_$w.err
+  res=$(dirname "$out")      # the directory the profiles above went to
+  python3 bench.py --full --workload $w --steps $steps --warmup 20 > $res/${TAG}_bench_$w.json 2> $res/${TAG}_bench_$w.err
   echo "== $w"; tail -c 900 gpurun_out/${TAG}_bench_$w.json; echo
 done
 # the secondary tables of the round (a change tuned on the headline configuration is re-measured where the kernel is actually used:

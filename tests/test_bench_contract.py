@@ -16,8 +16,29 @@ KEYS = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 def test_bench_help_lists_the_contract_flags():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--full", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_bench_dump_sample_is_bounded_and_seeded():
+    """--dump-outputs: an output above its share of the 64 MB is sampled, one element per block of 2^k at seeded offsets --
+    the same positions on every run -- and everything written stays within the budget"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    n = 1 << 24                                                        # 128 MB of complex64: must be sampled
+    y = torch.view_as_complex(torch.arange(2 * n, dtype=torch.float32).reshape(n, 2))
+    for world in (1, 2):
+        a = bench._snapshot({"y": y}, bench.DUMP_BYTES // world, torch)
+        b = bench._snapshot({"y": y}, bench.DUMP_BYTES // world, torch)
+        assert torch.equal(a["y"], b["y"]) and torch.equal(a["y_head"], torch.view_as_real(y[:bench.DUMP_HEAD]))
+        idx = a["y"][:, 0].numpy().astype(np.int64) // 2                   # (element i holds 2i, 2i + 1)
+        stride = n // len(idx)
+        assert n % len(idx) == 0 and np.array_equal(idx // stride, np.arange(len(idx))) and len(set(idx % stride)) > 1
+        assert sum(v.numel() * 4 + 128 for v in a.values()) <= bench.DUMP_BYTES // world
+    small = torch.ones(1000)
+    assert torch.equal(bench._snapshot({"y": small}, bench.DUMP_BYTES, torch)["y"], small)     # within the budget: whole
 
 
 def test_bench_reads_its_traffic_from_the_committed_pmc_file():
@@ -106,13 +127,15 @@ def _free_port():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
-def test_bench_two_ranks_self_launched(scaling):
+def test_bench_two_ranks_self_launched(scaling, tmp_path):
     """`python3 bench.py --gpus 2` with NO launcher in the command line (how the driver starts --gpus 1): bench.py launches
     its two ranks itself; rehearsed on ONE GPU over gloo like the test below.  strong: the 2^26 samples are split in two."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["TSDGPU_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", scaling],
-                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", scaling,
+                        "--dump-outputs", "out"],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
@@ -120,6 +143,54 @@ def test_bench_two_ranks_self_launched(scaling):
     assert d["n_gpus"] == 2 and d["scaling"] == scaling and d["value"] > 0
     assert d["config"]["backend"] == "gloo" and d["config"]["world_size"] == 2 and d["config"]["self_launched"] is True
     assert d["config"]["samples_per_gpu"] == (1 << 25 if scaling == "strong" else 1 << 26)
+    # every rank dumps its own outputs, under the directory given relative to the caller's working directory
+    files = sorted(f.name for f in dump.iterdir())
+    assert files == ["rank0_y.npy", "rank0_y_head.npy", "rank1_y.npy", "rank1_y_head.npy"], files
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path, orc):
+    """A plain run prints the headline only (no roofline replay, direct line or CPU baseline), `ms_per_step` is the time of one
+    of the --steps timed steps, and --dump-outputs writes what its last timed step computed: the FIR of the seeded input, checked against the oracle's
+    stateful FIR over two passes of the same block (every step filters the same resident block)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--log2n", "20",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert abs(d["ms_per_step"] - (1 << 20) / (d["value"] * 1e6) * 1e3) <= 1e-4         # (ms_per_step is rounded to 1e-4 ms)
+    for k in ("metric", "unit", "dtype"):
+        assert d[k]
+    assert not {"roofline", "direct", "cpu_baseline"} & set(d)
+    g = torch.Generator(device="cuda:0").manual_seed(2)
+    x = torch.view_as_complex(torch.randn(1 << 20, 2, device="cuda:0", generator=g)).cpu().numpy()
+    f = orc.Fir(bench.design_lowpass(bench.K_TAPS, 0.02))
+    f.step(x)
+    ref = f.step(x)
+    y = np.load(tmp_path / "y.npy")
+    head = np.load(tmp_path / "y_head.npy")
+    assert y.dtype == np.float32 and y.shape == (1 << 20, 2) and np.array_equal(head, y[:bench.DUMP_HEAD])
+    err = np.abs((y[:, 0] + 1j * y[:, 1]) - ref).max() / np.abs(ref).max()
+    assert err <= 1e-5, err
+
+
+@pytest.mark.gpu
+def test_bench_full_run_keeps_the_roofline_and_direct_lines():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "20",
+                        "--full", "--no-cpu"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    rf = d["roofline"]
+    assert rf["bound"] == "hbm" and rf["kernel_ms"] > 0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
+    assert rf["traffic"] is None and rf["traffic_source"] is None        # (the PMC passes were run at 2^26, not 2^20)
+    assert d["direct"]["value"] > 0 and "cpu_baseline" not in d
 
 
 @pytest.mark.gpu
