@@ -22,9 +22,12 @@ namespace tsdgpu {
 using namespace w1024;
 constexpr int OLS_N = 1024;
 // complex values of the kernel: float2 with scalar fp32 arithmetic; -DOLS_SCALAR=0 selects the
-// packed (VOP3P) flavour of fft1024_wave.hpp -- half the VALU instructions, parity-green, but
-// measured 2 % SLOWER (0.2313 vs 0.2260 ms, three interleaved runs): the kernel runs at the
-// speed of its memory skeleton, so the arithmetic is not what it waits for
+// packed (VOP3P) flavour of fft1024_wave.hpp -- half the VALU instructions, parity-green but not
+// bit-identical, and measured slower on the overlapping loop too (round 5: 0.2024 against 0.1938 ms
+// median of three interleaved runs; round 3, before it: 2 % slower)
+#ifndef OLS_SCALAR
+#define OLS_SCALAR 1
+#endif
 #ifndef OLS_RUN_DEFAULT   // blocks per run of a wave (ols_body): 1 = every block loads its whole overlap again
 #define OLS_RUN_DEFAULT 2
 #endif
@@ -33,11 +36,15 @@ constexpr int OLS_N = 1024;
 #endif
 constexpr int OLS_MAX_CTR = 32;
 // One wave per workgroup, the block's 46 per-lane constants (twiddles of the two radix-16 stages, the response H) in registers for
-// the wave's lifetime: 200 VGPRs, 2 waves per SIMD.  Measured against it and not kept (profiles/EXPERIMENTS.md, round 3): four
+// the wave's lifetime: 196-210 VGPRs, 2 waves per SIMD.  Measured against it and not kept (profiles/EXPERIMENTS.md, round 3): four
 // waves per workgroup with the tables in an LDS image (0.2081-0.2087 against 0.2017-0.2032 ms), twiddles generated from four
 // table entries per stage (0.2154-0.267), the packed VOP3P arithmetic of fft1024_wave.hpp (2 % slower), 16-B and non-temporal
 // global accesses.
+#if OLS_SCALAR
 using cv = cpx;
+#else
+using cv = v2f;
+#endif
 __device__ __forceinline__ cv mkv(float a, float b) { return Make<cv>::of(a, b); }
 
 // EDGE = false: block fully inside [0, n) on both the input and the output side -- no guards,
@@ -112,7 +119,8 @@ __device__ __forceinline__ void ols_fetch(cv (&v)[16], const cv *__restrict__ x,
 // pullers of one counter sit on all 8 XCDs; a pulled value v stands for unit v * NC + c.  The counters are never reset:
 // every launch starts from `base` (host-tracked) and advances each counter by exactly Q + G / NC -- Q = ceil(units / NC)
 // values inside the quota plus one failing pull per wave -- so the host knows the next launch's base without a memset.
-// The pull for the NEXT run is issued at the start of the current one: its latency hides under R blocks.
+// The pull for the NEXT run is issued behind the prefetch loads of the block that prefetches the current run's first block,
+// and its value is taken with that prefetch, before the block's stores: its latency hides under a transform.
 struct OlsDyn {
   unsigned *ctr;
   unsigned base, Q;
@@ -161,17 +169,27 @@ __device__ __forceinline__ void ols_body(cv *lds, const void *__restrict__ xv, c
   const int64_t slot = (G % 8 == 0) ? (w % 8) * (G / 8) + w / 8 : w;
   const int ctr_c = DYN ? (int) (cgrp % dyn.NC) : 0;     // cgrp: rounds of 8 workgroups (one per XCD)
   // -> the next unit of this wave's counter, or -1 once its quota is spent (exactly one failing pull per wave)
-  // (measured, round 4: issuing the pull a block earlier than its value is taken -- what pays in the resampler, whose loop
-  // otherwise drains its LDS-DMA at the pull -- costs 2 % here: 0.2057 against 0.2015 ms, three interleaved pairs)
+  // (measured, round 4, on the loop whose pull followed the stores: issuing the pull a block earlier than its value is taken
+  // costs 2 % here: 0.2057 against 0.2015 ms, three interleaved pairs)
+  auto pull_issue = [&]() -> unsigned {
+    unsigned v = 0;
+    if (lane == 0) v = __hip_atomic_fetch_add(dyn.ctr + ctr_c * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return v;
+  };
   auto pull = [&]() -> int64_t {
     for (;;) {
-      unsigned v = 0;
-      if (lane == 0) v = __hip_atomic_fetch_add(dyn.ctr + ctr_c * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      v = (unsigned) __builtin_amdgcn_readfirstlane((int) v) - dyn.base;
+      const unsigned v = (unsigned) __builtin_amdgcn_readfirstlane((int) pull_issue()) - dyn.base;
       if (v >= dyn.Q) return -1;
       const int64_t u = (int64_t) v * dyn.NC + ctr_c;
       if (u < dyn.nunits) return u;                  // (the last row of units may be partial: pull again)
     }
+  };
+  // the value of an atomic issued by pull_issue(), pulling again if it lands in the partial last row
+  auto pull_finish = [&](unsigned raw) -> int64_t {
+    const unsigned v = (unsigned) __builtin_amdgcn_readfirstlane((int) raw) - dyn.base;
+    if (v >= dyn.Q) return -1;
+    const int64_t u = (int64_t) v * dyn.NC + ctr_c;
+    return u < dyn.nunits ? u : pull();
   };
   int64_t unit = EDGE ? 0 : (DYN ? pull() : slot);
   if (unit < 0) return;
@@ -180,52 +198,78 @@ __device__ __forceinline__ void ols_body(cv *lds, const void *__restrict__ xv, c
   if (b >= b_hi) return;
 
   // One block: prefetch the next block into `nxt`, transform `cur` in place, then store it.
-  // Memory-queue discipline (vmcnt retires in issue order and hipcc waits vmcnt(0) around the
-  // predicated stores): the wait for the prefetch is forced BEFORE this block's stores are
-  // issued -- the loads are a whole block old by then, so it costs nothing -- and afterwards
-  // nothing waits on the stores: they drain while the next block is being transformed.
+  // Memory-queue discipline (vmcnt retires in issue order): the wait for the prefetch is forced
+  // BEFORE this block's stores are issued -- the loads are a whole block old by then, so it costs
+  // nothing -- and afterwards nothing waits on the stores: they drain while the next block is
+  // being transformed.  That wait is taken on EVERY path of an interior block, the last one
+  // included: were it skipped on one path, hipcc's wait-count insertion would merge the two
+  // states at the join and count the prefetch as still in flight, and the next block would then
+  // wait vmcnt(0) (its stores and the fresh prefetch) before its overlap copy and inside the head
+  // of its transform.  For the same reason the work-counter atomic is issued here, right behind
+  // the prefetch loads of a run's last block, and its value taken with the prefetch: a pull after
+  // the stores would make its vmcnt(0) drain them.
   // nb: the block prefetched while `blk` is transformed; inrun: nb = blk + 1 inside the same run
+  int64_t pulled = -1;   // DYN: the run after the one the last run-ending block prefetched (-1: none left)
   auto process = [&](cv (&cur)[16], cv (&nxt)[16], int64_t blk, int64_t nb, bool inrun) {
     const bool more = !EDGE && nb < b_hi;
-    // the prefetch of block nb into `nxt`: the rows reused from this block are copied NOW (cur still holds the raw samples),
-    // the loads are issued at `prefetch_loads()` -- before the forward transform
-    if (more && R0 > 0 && inrun) {
+    // the prefetch of block nb into `nxt`, issued before the forward transform.  Interior blocks always load rows R0 .. 15 (a
+    // wave's last block, !more, loads its own block again: in bounds, an L2 hit), so that no path of the loop skips them; rows
+    // 0 .. R0-1 are the R0 rows reused from this block inside a run (saved in `keep` now, while cur still holds the raw
+    // samples) and are loaded into `pre` otherwise.  Both land in nxt only after the wait for the prefetch below.  Neither
+    // is written into nxt here on one path while the other path loads into it: hipcc's wait-count insertion would merge the
+    // two paths and put a vmcnt(0) -- the previous block's stores and the fresh prefetch -- in front of that write.
+    cv keep[R0 > 0 ? R0 : 1], pre[R0 > 0 ? R0 : 1];
 #pragma unroll
-      for (int r = 0; r < R0; r++) nxt[r] = REAL ? mkv(cur[(16 - R0 + r) & 15].y, 0.f) : cur[(16 - R0 + r) & 15];
-    }
-    auto prefetch_loads = [&]() {
-      if (!more) return;
-      if (R0 > 0 && inrun) {
-        if (!REAL) {
-          const cv *xb = x + (nb * (int64_t) L - Km1);
+    for (int r = 0; r < R0; r++) keep[r] = cur[(16 - R0 + r) & 15];
+    const int64_t pb = more ? nb : blk;
+    if (!EDGE && R0 > 0) {
+      if (!REAL) {
+        const cv *xb = x + (pb * (int64_t) L - Km1);
+        if (!inrun) {
 #pragma unroll
-          for (int r = R0; r < 16; r++) nxt[r] = NT ? ntload(xb + 64 * r + lane) : xb[64 * r + lane];
-        } else {
-          // pair (2 nb, 2 nb + 1): the first block's overlap is the tail of this pair's second block; the second block's
-          // overlap is the tail of the first block being loaded now -- filled in once the loads have landed (below)
-          const float *xa = xr + (2 * nb * (int64_t) L - Km1), *xb = xa + L;
-#pragma unroll
-          for (int r = R0; r < 16; r++) nxt[r] = mkv(xa[64 * r + lane], xb[64 * r + lane]);
+          for (int r = 0; r < R0; r++) pre[r] = xb[64 * r + lane];
         }
-      } else if (REAL) ols_fetch_real<EDGE>(nxt, xr, histr, histlen, Km1, L, n, nb, lane);
-      else ols_fetch<EDGE>(nxt, x, hist, histlen, Km1, L, n, nb, lane);
-    };
-    prefetch_loads();
+#pragma unroll
+        for (int r = R0; r < 16; r++) nxt[r] = NT ? ntload(xb + 64 * r + lane) : xb[64 * r + lane];
+      } else {
+        // pair (2 pb, 2 pb + 1): inside a run, the first block's overlap is the tail of this pair's second block and the second
+        // block's overlap the tail of the first block being loaded now -- both put in place once the loads have landed
+        const float *xa = xr + (2 * pb * (int64_t) L - Km1), *xb = xa + L;
+        if (!inrun) {
+#pragma unroll
+          for (int r = 0; r < R0; r++) pre[r] = mkv(xa[64 * r + lane], xb[64 * r + lane]);
+        }
+#pragma unroll
+        for (int r = R0; r < 16; r++) nxt[r] = mkv(xa[64 * r + lane], xb[64 * r + lane]);
+      }
+    } else if (!EDGE) {
+      if (REAL) ols_fetch_real<EDGE>(nxt, xr, histr, histlen, Km1, L, n, pb, lane);
+      else ols_fetch<EDGE>(nxt, x, hist, histlen, Km1, L, n, pb, lane);
+    }
+    const bool pulls = DYN && more && !inrun;   // nb starts the next run: pull the run after it
+    unsigned raw = 0;
+    if (pulls) raw = pull_issue();
     forward(cur, lds, lane, tw1r, tw2r, sync);
 #pragma unroll
     for (int r = 0; r < 16; r++) cur[r] = cmul(cur[r], Hr[r]);
     inverse(cur, lds, lane, tw1r, tw2r, sync);
     sync();   // LDS is reused by the next block
-    if (more) {
+    if (!EDGE) {
+      // the wait for the prefetch (rows 0 .. R0-1 of `pre` are issued before the others: vmcnt retires in order)
 #pragma unroll
-      for (int r = 0; r < 16; r++) asm volatile("" ::"v"(nxt[r]));
-      if (REAL && R0 > 0 && inrun) {
+      for (int r = R0; r < 16; r++) asm volatile("" ::"v"(nxt[r]));
 #pragma unroll
-        for (int r = 0; r < R0; r++) nxt[r].y = nxt[(16 - R0 + r) & 15].x;
+      for (int r = 0; r < R0; r++) {
+        asm volatile("" : "+v"(keep[r]));   // (keep stays live to here on every path: never in a register the loads write)
+        if (inrun) nxt[r] = REAL ? mkv(keep[r].y, nxt[(16 - R0 + r) & 15].x) : keep[r];
+        else nxt[r] = pre[r];
       }
     }
+    if (pulls) pulled = pull_finish(raw);
     // sample t = 64*r + lane of the circular convolution is output o0 + t - (K-1)
-    const int r0 = Km1 >> 6;   // Km1 is a multiple of 64: rows below r0 are overlap, the rest whole
+    // Km1 is a multiple of 64: rows below r0 are overlap, the rest whole (R0 > 0: the launch has exactly R0 overlap rows, and
+    // the interior's stores are unconditional)
+    const int r0 = (!EDGE && R0 > 0) ? R0 : Km1 >> 6;
     if (!REAL) {
       const int64_t o0 = blk * (int64_t) L;
       cv *yb = y + (o0 - Km1);
@@ -261,14 +305,19 @@ __device__ __forceinline__ void ols_body(cv *lds, const void *__restrict__ xv, c
     process(A, B, b, b_hi, false);   // edge launches: one block per wave, no prefetch
     return;
   }
+  // the first block is waited for here, before the loop: left in flight into it, the loop head would merge "A in flight"
+  // with the back-edge's "A landed", and every block's transform would start with a vmcnt(0) (its predecessor's stores)
+#pragma unroll
+  for (int r = 0; r < 16; r++) asm volatile("" ::"v"(A[r]));
   int i = 0;                        // position of b inside its run
   constexpr int64_t END = INT64_MAX;
-  // the run after the current one (requested one run ahead)
+  // the run after the current one (requested one run ahead; DYN: pulled by the block that prefetches the current run's first
+  // block, see process)
   auto unit_after = [&](int64_t u) -> int64_t {
-    if (DYN) return pull();
+    if (DYN) return pulled;
     return b_lo + (u + G) * R < b_hi ? u + G : -1;
   };
-  int64_t unit_next = unit_after(unit);
+  int64_t unit_next = DYN ? pull() : unit_after(unit);
   auto next_of = [&](int64_t &nb, bool &inrun) {
     inrun = i + 1 < R && b + 1 < b_hi;
     nb = inrun ? b + 1 : (unit_next >= 0 ? b_lo + unit_next * R : END);
