@@ -79,6 +79,14 @@ bool host_ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
 // small device-to-device copy as a kernel launch (see common.hip)
 int device_copy_small(void *dst, const void *src, size_t bytes, hipStream_t st);
 bool host_pipe_enabled();     // false with TSDGPU_NO_PIPE=1 (A/B switch: whole-vector staging instead)
+// What the block-parallel recursions may leave out of the filter state, relative to the state (so after a loud burst the
+// dropped part is compared with whatever quiet signal follows).  Chunk warm-ups from zero state stop where the state
+// transition is below STATE_TAIL_BOUND.  The SOS scans stop at the level whose power is below SCAN_TAIL_BOUND: at 1e-9 the
+// dropped levels left 2.3e-4 of a quiet window's peak 120 dB after a burst (tests/test_dynamic_range_gpu.py, 4th order at
+// 0.02); at 1e-13 that case sits within 5x libtsd's own error.  Tightening the warm-ups as well doubles cfg 4's W (256 -> 512)
+// for 4.5 % of its step time and moves no measured case.
+constexpr double STATE_TAIL_BOUND = 1e-9;
+constexpr double SCAN_TAIL_BOUND = 1e-13;
 // Developer / test switches: plan overrides and hand-out thresholds that let the tests put an ALTERNATIVE PRODUCT PATH (the static
 // partition of a dynamic kernel, the plan another size would take, the literal recursion ...) under the parity tests at small
 // sizes (scripts/check_switches.sh).  One door for all of them: dev_switch("FFT_NO_SMOOTH") is the environment variable

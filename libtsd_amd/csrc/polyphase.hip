@@ -552,7 +552,7 @@ int sos_create_ex(tsdgpu_sos **out, int data_type, const float *coefs_host, int 
 // Kogge-Stone scan of the affine maps y -> a y + e, a = r^16 the same for every lane, so only e travels (6 shuffle steps
 // against the host-made powers a^(2^k)); every sample then gets its carry: c <- r c, y += c.  A wave walks the sub-tiles of
 // its chunk carrying the sections' states exactly; chunk 0 starts from the stream's state, the others `warm` sub-tiles
-// early from zero state, the host having found the warm-up after which the cascade's memory is below 1e-9.
+// early from zero state, the host having found the warm-up after which the cascade's memory is below STATE_TAIL_BOUND.
 // tab[s][8] = r, a, a^2, a^4, a^8, a^16, a^32, (pad).
 constexpr int C1_LANE = 16, C1_SUB = 64 * C1_LANE, C1_PITCH = C1_LANE + 2;     // pitch 18 complex = 144 B: conflict-free b128
 constexpr int C1_MAX_SEC = 16;
@@ -1141,7 +1141,7 @@ bool factor_denominator_c(const float *den2, int Kd, std::vector<cd> &poles)
   std::sort(poles.begin(), poles.end(), [](const cd &a, const cd &b) { return std::abs(a) > std::abs(b); });
   return true;
 }
-// samples after which the cascade's memory is below 1e-9: the zero-input response from every unit state, in double
+// samples after which the cascade's memory is below STATE_TAIL_BOUND: the zero-input response from every unit state, in double
 int64_t cascade_c_warmup(const std::vector<cd> &poles, int64_t limit)
 {
   const int p = (int) poles.size();
@@ -1159,7 +1159,7 @@ int64_t cascade_c_warmup(const std::vector<cd> &poles, int64_t limit)
         mx = std::max(mx, std::abs(v));
       }
       n++;
-      calme = mx < 1e-9 ? calme + 1 : 0;
+      calme = mx < STATE_TAIL_BOUND ? calme + 1 : 0;
     }
     if (n >= limit) return -1;
     W = std::max(W, n);

@@ -2,7 +2,7 @@
 // operator handle per chunk, and the ONE small left-neighbour halo each operator needs
 // (north_star: "long vectors shard by contiguous chunk with halo exchange"):
 //   FIR        the K-1 input samples before the chunk           -> tsdgpu_fir_set_history
-//   SOS        W warm-up samples (state transition < 1e-9)      -> reset + step on the halo
+//   SOS        W warm-up samples (state transition < STATE_TAIL_BOUND) -> reset + step on the halo
 //   resampler  the K-1-sample window + the absolute position    -> tsdgpu_resampler_seek
 // No collective and no data-path exchange beyond those few samples: shards run concurrently, one
 // host thread and one stream per shard.  Two forms:

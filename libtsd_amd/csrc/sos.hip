@@ -20,7 +20,7 @@
 //  * a wave walks a chunk of consecutive sub-tiles carrying the state exactly; chunk 0 starts
 //    from the stream state carried by the handle, every other chunk starts W samples early
 //    from zero state, W chosen on the host so that the cascade's state-transition matrix
-//    satisfies ||Phi^W||_inf <= 1e-9 (chunks are >= 4 W long; a filter that decays slowly
+//    satisfies ||Phi^W||_inf <= STATE_TAIL_BOUND (chunks are >= 4 W long; a filter that decays slowly
 //    simply gets fewer, longer chunks -- down to a single sequential one);
 //  * global accesses are 16 B per lane, transposed lane<->sample through padded LDS.
 #include "common.hpp"
@@ -56,8 +56,8 @@ struct SosSection {
   float An[6][4];
   float c1n[NARROW_FLOATS], c2n[NARROW_FLOATS];
   // Levels of the Kogge-Stone scan that matter: after K levels a lane's sum holds the terms of the 2^K lanes before it, and
-  // the first term left out is (M^L)^(2^K) Z = A[K] Z -- below 1e-9 of the states for a damped section long before the sixth
-  // level (pole radius 0.88: three levels; 0.67: two; 0.5 and less: one).  The bound of the chunk warm-ups (||Phi^W|| <= 1e-9).
+  // the first term left out is (M^L)^(2^K) Z = A[K] Z -- below SCAN_TAIL_BOUND of the states for a damped section long before the sixth
+  // level (pole radius 0.88: three levels; 0.67: two; 0.5 and less: one).  (The chunk warm-ups use STATE_TAIL_BOUND, common.hpp.)
   int nlev, nlevn;
 };
 
@@ -213,7 +213,7 @@ __device__ __forceinline__ void sos_cascade(float (&v)[LF], const SosSection *__
 // Chunk c owns sub-tiles [c spc, (c+1) spc).  Chunk 0 starts from the stream state; every other chunk
 // starts from zero state `warm_sub` whole sub-tiles plus `warm_nar` narrow steps (256 floats each, one
 // 16-B load per lane, a 4-float recurrence per lane and section: a fifth of a sub-tile's work) before
-// its first sample -- the host picks them so that the state transition over the warm-up is below 1e-9.
+// its first sample -- the host picks them so that the state transition over the warm-up is below STATE_TAIL_BOUND.
 //
 // MODE 0 is that scheme.  A filter whose memory is long against the call (a DC blocker, a smoother with a cut-off of
 // 1e-4: warm-ups of 10^5 samples and more, or no decay at all) would leave it a handful of chunks -- down to ONE wave
@@ -520,7 +520,7 @@ struct tsdgpu_sos {
   float *d_state[2] = {nullptr, nullptr};
   int cur = 0;
   bool capturable = false;      // tsdgpu_sos_set_capturable: the state is back in d_state[0] after every step
-  int64_t halo = 0;             // W: samples after which the state transition is below 1e-9
+  int64_t halo = 0;             // W: samples after which the state transition is below STATE_TAIL_BOUND
   int64_t skip_f = 0;           // tsdgpu_sos_step_skip: floats at the start of the current call that are filtered but not stored
   DevBuf in_stage, out_stage;
   // exact carry of the state from chunk to chunk (long-memory filters, see sos_kernel)
@@ -567,7 +567,7 @@ int64_t compute_halo(const std::vector<SosSection> &sec)
       for (int j = 0; j < m; j++) r += std::fabs(P[(size_t) i * m + j]);
       nrm = std::max(nrm, r);
     }
-    if (!(nrm > 1e-9)) return W;
+    if (!(nrm > STATE_TAIL_BOUND)) return W;
     if (!std::isfinite(nrm)) break;
     std::vector<double> Q((size_t) m * m, 0.0);
     for (int i = 0; i < m; i++)
@@ -712,14 +712,14 @@ void fill_tables_for(SosSection &k, int L, int NF, float *c1o, float *c2o, float
     for (int j = 0; j < 4; j++) A[j] = t[j];
   }
 }
-// scan levels that matter for this table (see SosSection::nlev): the first K whose power is below 1e-9 in the row-sum norm
+// scan levels that matter for this table (see SosSection::nlev): the first K whose power is below SCAN_TAIL_BOUND in the row-sum norm
 int scan_levels(const float (*A)[4])
 {
   static const bool full = dev_switch("SOS_FULL_SCAN") != nullptr;      // A/B and test switch: all six levels
   if (full) return 6;
   for (int K = 0; K < 6; K++) {
     const double n0 = std::fabs((double) A[K][0]) + std::fabs((double) A[K][1]), n1 = std::fabs((double) A[K][2]) + std::fabs((double) A[K][3]);
-    if (std::isfinite(n0) && std::isfinite(n1) && std::max(n0, n1) <= 1e-9) return K;
+    if (std::isfinite(n0) && std::isfinite(n1) && std::max(n0, n1) <= SCAN_TAIL_BOUND) return K;
   }
   return 6;
 }

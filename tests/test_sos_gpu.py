@@ -308,16 +308,8 @@ def test_sos_long_memory_forme_directe_1(tg, orc, cplx, order, fc):
     y = g.step(x)
     # the float64 run of the same chain arbitrates (FormeDirecte1 seeds all four memories of a section with its first input,
     # filtre-rt.cc:361-365; the trailing first-order section starts from zero and carries the gain, :407-437,567-570)
-    from scipy.signal import lfilter, lfiltic
-    v = x.astype(np.complex128 if cplx else np.float64)
-    for b0, b1, b2, a1, a2 in np.asarray(co, np.float32).astype(np.float64).reshape(-1, 5):
-        zi = lfiltic([b0, b1, b2], [1.0, a1, a2], y=[v[0], v[0]], x=[v[0], v[0]])
-        v, _ = lfilter([b0, b1, b2], [1.0, a1, a2], v, zi=zi.astype(v.dtype))
-    if r1 is not None:
-        q = np.asarray(r1, np.float32).astype(np.float64)
-        v = lfilter([q[0], q[1]], [1.0, q[2]], v)
-    else:
-        v = v * np.float64(np.float32(gain))
+    import f64ref
+    v = f64ref.sos(co, gain, r1, x, forme=1)
     noise = relerr(yref, v)
     print("long memory DF1", order, fc, cplx, "err", relerr(y, v), "reference's own", noise)
     assert relerr(y, v) <= max(2e-5, noise), (relerr(y, v), noise)
