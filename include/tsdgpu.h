@@ -243,6 +243,45 @@ int tsdgpu_sos_propagate_state(const tsdgpu_sos *s, int64_t n_samples, const flo
 int tsdgpu_sos_destroy(tsdgpu_sos *s);
 
 /* --------------------------------------------------------------------------------------
+ * Channel banks: C streams of ONE filter, filtered in one launch per step.  An extension: libtsd
+ * has no multichannel filter; a bank stands behind FiltreRIF<T,Tc>::step (filtre-rt.cc:53-109)
+ * or ChaineSOIS<T,T,T>::step (:303-400, 440-572) applied to each column of an n x C
+ * column-major Tab.
+ *  - layout: channel c of a step reads x + c*ldx and writes y + c*ldy, n samples each (ld in
+ *    samples, ld >= n, the same n for every channel).  ld = n is the storage of libtsd's n x C
+ *    Tab; ld > n a row-strided (C, ld) view.  Channel offsets are 64-bit: C*ld may pass 2^31.
+ *  - channel c behaves exactly like its own tsdgpu_fir / tsdgpu_sos handle fed the same
+ *    blocks: zero FIR history at creation, state carried across steps, the SOS first-sample
+ *    seed applied per channel on that channel's own first sample (filtre-rt.cc:361-365).
+ *  - n == 0 is a no-op.  In place: x == y with ldx == ldy; any other overlap of x and y is
+ *    TSDGPU_ERR_INVALID.  Host or device pointers (host buffers staged with 2-D copies);
+ *    streams as everywhere in this header.  The fast path takes 16-B aligned channel bases
+ *    (aligned x / y, ld * sizeof(sample) % 16 == 0); other layouts are served as well.
+ *  - create: the argument checks of tsdgpu_fir_create / tsdgpu_sos_create, plus channels >= 1
+ *    (TSDGPU_ERR_INVALID).  A FIR bank always runs the direct scheme: more than 12289 taps is
+ *    TSDGPU_ERR_UNSUPPORTED.  Each channel's output is bit-identical to a TSDGPU_FIR_DIRECT handle.
+ * ------------------------------------------------------------------------------------ */
+typedef struct tsdgpu_fir_bank tsdgpu_fir_bank;
+int tsdgpu_fir_bank_create(tsdgpu_fir_bank **out, int data_type, int tap_type, const void *taps_host, int ntaps, int channels);
+int tsdgpu_fir_bank_step(tsdgpu_fir_bank *b, const void *x, int64_t ldx, void *y, int64_t ldy, int64_t n, void *stream);
+int tsdgpu_fir_bank_reset(tsdgpu_fir_bank *b);           /* every history <- zeros */
+/* dst / src: channels x (ntaps-1) samples, channel-major, oldest first (tsdgpu_fir_get_history per channel); host or device */
+int tsdgpu_fir_bank_get_history(tsdgpu_fir_bank *b, void *dst, void *stream);
+int tsdgpu_fir_bank_set_history(tsdgpu_fir_bank *b, const void *src, void *stream);
+int tsdgpu_fir_bank_destroy(tsdgpu_fir_bank *b);
+
+typedef struct tsdgpu_sos_bank tsdgpu_sos_bank;
+int tsdgpu_sos_bank_create(tsdgpu_sos_bank **out, int data_type, const float *coefs_host, int nsec, float gain,
+                           const float *rii1_host, int forme, int channels);
+int tsdgpu_sos_bank_step(tsdgpu_sos_bank *b, const void *x, int64_t ldx, void *y, int64_t ldy, int64_t n, void *stream);
+int tsdgpu_sos_bank_reset(tsdgpu_sos_bank *b);           /* every channel back to its state at creation (seed pending) */
+/* one channel's memories in the record layout of tsdgpu_sos_get_state (tsdgpu_sos_state_floats() floats), host buffer: a
+ * channel moves between a bank and a tsdgpu_sos handle of the same chain; channel outside [0, C) is TSDGPU_ERR_INVALID */
+int tsdgpu_sos_bank_get_state(tsdgpu_sos_bank *b, int channel, float *state_host, void *stream);
+int tsdgpu_sos_bank_set_state(tsdgpu_sos_bank *b, int channel, const float *state_host, void *stream);
+int tsdgpu_sos_bank_destroy(tsdgpu_sos_bank *b);
+
+/* --------------------------------------------------------------------------------------
  * Resampler:  AdaptationRythmeSimple<T>::step (factory filtre_itrp) over
  *             InterpolateurRIF::step with the LUT-sinc interpolator itrp_sinc
  *             (src/reechan/ra.cc:13-79; include/tsd/filtrage.hpp:1873-1881;

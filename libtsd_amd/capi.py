@@ -70,6 +70,18 @@ def _declare(L):
     L.tsdgpu_sos_halo.argtypes = [vp]
     L.tsdgpu_sos_halo.restype = i64
     L.tsdgpu_sos_destroy.argtypes = [vp]
+    L.tsdgpu_fir_bank_create.argtypes = [C.POINTER(vp), i32, i32, vp, i32, i32]
+    L.tsdgpu_fir_bank_step.argtypes = [vp, vp, i64, vp, i64, i64, vp]
+    L.tsdgpu_fir_bank_reset.argtypes = [vp]
+    L.tsdgpu_fir_bank_get_history.argtypes = [vp, vp, vp]
+    L.tsdgpu_fir_bank_set_history.argtypes = [vp, vp, vp]
+    L.tsdgpu_fir_bank_destroy.argtypes = [vp]
+    L.tsdgpu_sos_bank_create.argtypes = [C.POINTER(vp), i32, vp, i32, fl, vp, i32, i32]
+    L.tsdgpu_sos_bank_step.argtypes = [vp, vp, i64, vp, i64, i64, vp]
+    L.tsdgpu_sos_bank_reset.argtypes = [vp]
+    L.tsdgpu_sos_bank_get_state.argtypes = [vp, i32, vp, vp]
+    L.tsdgpu_sos_bank_set_state.argtypes = [vp, i32, vp, vp]
+    L.tsdgpu_sos_bank_destroy.argtypes = [vp]
     L.tsdgpu_resampler_create.argtypes = [C.POINTER(vp), i32, fl, vp, i32, i32]
     L.tsdgpu_resampler_out_count.argtypes = [vp, i64]
     L.tsdgpu_resampler_out_count.restype = i64
@@ -176,6 +188,30 @@ def _ptr(a):
     if not a.is_contiguous():
         raise TsdGpuError("non-contiguous tensor: pass x.contiguous()")
     return a.data_ptr()
+
+
+def _ptr2d(a, channels):
+    """(address, row stride in samples) of a 2-D (channels, n) numpy array or torch tensor for the channel banks: packed
+    float32 / complex64 rows (stride(-1) == 1), row stride >= n.  Anything else is refused instead of being reinterpreted."""
+    _dtype_code(a)
+    if a.ndim != 2:
+        raise TsdGpuError(f"a channel bank takes a 2-D (channels, n) array, got {a.ndim}-D")
+    C_, n = a.shape
+    if C_ != channels:
+        raise TsdGpuError(f"{C_} rows for a bank of {channels} channels")
+    if isinstance(a, np.ndarray):
+        if a.strides[0] % a.itemsize or a.strides[1] % a.itemsize:
+            raise TsdGpuError("row stride is not a whole number of samples")
+        s0, s1, ptr = a.strides[0] // a.itemsize, a.strides[1] // a.itemsize, a.ctypes.data
+    else:
+        s0, s1, ptr = a.stride(0), a.stride(1), a.data_ptr()
+    if n > 1 and s1 != 1:
+        raise TsdGpuError("samples of a channel must be contiguous (stride(-1) == 1): pass x.contiguous()")
+    if C_ == 1:
+        s0 = max(s0, n)
+    if s0 < n:
+        raise TsdGpuError(f"row stride {s0} below the row length {n} (rows overlap, or a column-major view)")
+    return ptr, s0
 
 
 def _dtype_code(a):
@@ -531,6 +567,107 @@ class Sos:
     def close(self):
         if self._h:
             lib().tsdgpu_sos_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bank_out(x, y):
+    if y is None:
+        return np.empty(x.shape, x.dtype) if isinstance(x, np.ndarray) else x.new_empty(x.shape)
+    if tuple(y.shape) != tuple(x.shape):
+        raise TsdGpuError(f"output shape {tuple(y.shape)} differs from the input's {tuple(x.shape)}")
+    return y
+
+
+class FirBank:
+    """C channels of filtre_rif<Tc,T>(h) in one launch per step (tsdgpu_fir_bank): step(x) filters a (C, n) block, row c
+    being channel c; every channel bit-identical to its own Fir(h, data_type, FIR_DIRECT) fed the same blocks."""
+
+    def __init__(self, taps, data_type, channels):
+        taps = np.ascontiguousarray(taps)
+        tt = C64 if np.iscomplexobj(taps) else F32
+        taps = taps.astype(np.complex64 if tt == C64 else np.float32)
+        self.K, self.data_type, self.channels = len(taps), data_type, int(channels)
+        self._h = C.c_void_p()
+        _check(lib().tsdgpu_fir_bank_create(C.byref(self._h), data_type, tt, taps.ctypes.data, len(taps), self.channels))
+
+    def step(self, x, y=None, stream=None):
+        """x: (C, n) numpy array (host) or torch tensor (host or device), float32 / complex64, rows may be strided."""
+        assert _dtype_code(x) == self.data_type, "input dtype does not match the bank's data type"
+        y = _bank_out(x, y)
+        px, ldx = _ptr2d(x, self.channels)
+        py, ldy = _ptr2d(y, self.channels)
+        _check(lib().tsdgpu_fir_bank_step(self._h, px, ldx, py, ldy, int(x.shape[1]), _stream_of(x, stream)))
+        return y
+
+    def reset(self):
+        _check(lib().tsdgpu_fir_bank_reset(self._h))
+
+    def get_history(self, dst=None, stream=None):
+        """(C, K-1) samples, oldest first per channel; dst: packed numpy array or torch tensor (default: a new numpy array)."""
+        if dst is None:
+            dst = np.zeros((self.channels, max(self.K - 1, 0)), np.complex64 if self.data_type == C64 else np.float32)
+        assert tuple(dst.shape) == (self.channels, max(self.K - 1, 0)) and _dtype_code(dst) == self.data_type
+        _check(lib().tsdgpu_fir_bank_get_history(self._h, _ptr(dst), _stream_of(dst, stream)))
+        return dst
+
+    def set_history(self, src, stream=None):
+        assert tuple(src.shape) == (self.channels, max(self.K - 1, 0)) and _dtype_code(src) == self.data_type
+        _check(lib().tsdgpu_fir_bank_set_history(self._h, _ptr(src), _stream_of(src, stream)))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_fir_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SosBank:
+    """C channels of one SOS chain (Sos's arguments) in one launch per step (tsdgpu_sos_bank); each channel seeds its
+    sections on its own first sample.  get_state(c) / set_state(c, s): the record of Sos.get_state / Sos.set_state."""
+
+    def __init__(self, coefs, gain, data_type, channels, rii1=None, forme=2):
+        coefs = np.ascontiguousarray(coefs, dtype=np.float32).reshape(-1, 5)
+        self.data_type, self.channels = data_type, int(channels)
+        self._h = C.c_void_p()
+        r1 = None if rii1 is None else np.ascontiguousarray(rii1, dtype=np.float32)
+        _check(lib().tsdgpu_sos_bank_create(C.byref(self._h), data_type, coefs.ctypes.data, coefs.shape[0], float(gain),
+                                            None if r1 is None else r1.ctypes.data, forme, self.channels))
+
+    def step(self, x, y=None, stream=None):
+        assert _dtype_code(x) == self.data_type, "input dtype does not match the bank's data type"
+        y = _bank_out(x, y)
+        px, ldx = _ptr2d(x, self.channels)
+        py, ldy = _ptr2d(y, self.channels)
+        _check(lib().tsdgpu_sos_bank_step(self._h, px, ldx, py, ldy, int(x.shape[1]), _stream_of(x, stream)))
+        return y
+
+    def reset(self):
+        _check(lib().tsdgpu_sos_bank_reset(self._h))
+
+    def get_state(self, channel, stream=None):
+        st = np.zeros(lib().tsdgpu_sos_state_floats(), np.float32)
+        _check(lib().tsdgpu_sos_bank_get_state(self._h, int(channel), st.ctypes.data, stream))
+        return st
+
+    def set_state(self, channel, state, stream=None):
+        st = np.ascontiguousarray(state, dtype=np.float32)
+        assert st.size == lib().tsdgpu_sos_state_floats()
+        _check(lib().tsdgpu_sos_bank_set_state(self._h, int(channel), st.ctypes.data, stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_sos_bank_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -22,26 +22,6 @@
 
 namespace tsdgpu {
 
-// ------------------------------------------------------------------ arithmetic helpers
-__device__ __forceinline__ float zero_of(float) { return 0.f; }
-__device__ __forceinline__ float2 zero_of(float2) { return make_float2(0.f, 0.f); }
-
-// acc += x * h for the three (data, tap) combinations of the reference
-__device__ __forceinline__ float mac(float acc, float x, float h) { return fmaf(x, h, acc); }
-__device__ __forceinline__ float2 mac(float2 acc, float2 x, float h)
-{
-  return make_float2(fmaf(x.x, h, acc.x), fmaf(x.y, h, acc.y));
-}
-__device__ __forceinline__ float2 mac(float2 acc, float2 x, float2 h)
-{
-  // (xr + j xi)(hr + j hi), limited-range product as in the reference build
-  float re = fmaf(x.x, h.x, acc.x);
-  re = fmaf(-x.y, h.y, re);
-  float im = fmaf(x.x, h.y, acc.y);
-  im = fmaf(x.y, h.x, im);
-  return make_float2(re, im);
-}
-
 // ------------------------------------------------------------------ direct kernel
 // LDS image: the lane's R samples (64 B) form one segment, segments are 80 B apart (16 B of
 // padding): 80 B = 5 x 16 B, so the 16 lanes a ds_read_b128 / ds_write_b128 services together

@@ -34,6 +34,26 @@ struct tsdgpu_fir {
 };
 
 namespace tsdgpu {
+// ------------------------------------------------------------------ arithmetic helpers
+__device__ __forceinline__ float zero_of(float) { return 0.f; }
+__device__ __forceinline__ float2 zero_of(float2) { return make_float2(0.f, 0.f); }
+
+// acc += x * h for the three (data, tap) combinations of the reference
+__device__ __forceinline__ float mac(float acc, float x, float h) { return fmaf(x, h, acc); }
+__device__ __forceinline__ float2 mac(float2 acc, float2 x, float h)
+{
+  return make_float2(fmaf(x.x, h, acc.x), fmaf(x.y, h, acc.y));
+}
+__device__ __forceinline__ float2 mac(float2 acc, float2 x, float2 h)
+{
+  // (xr + j xi)(hr + j hi), limited-range product as in the reference build
+  float re = fmaf(x.x, h.x, acc.x);
+  re = fmaf(-x.y, h.y, re);
+  float im = fmaf(x.x, h.y, acc.y);
+  im = fmaf(x.y, h.x, im);
+  return make_float2(re, im);
+}
+
 inline const void *fir_hist_read(const tsdgpu_fir *f) { return f->hist_ext ? f->hist_ext : f->hist[f->cur]; }
 int fir_direct_step(tsdgpu_fir *f, const void *x, void *y, int64_t n, hipStream_t st);
 int fir_update_history(tsdgpu_fir *f, const void *x, int64_t n, hipStream_t st);

@@ -19,6 +19,7 @@
 #include <complex>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -72,6 +73,56 @@ struct TamponGpu {
     return p;
   }
 };
+
+// ---- ChaineSOIS' sections from a pole / zero fraction (filtre-rt.cc:440-572) -------------------------
+// Greedy conjugate pairing as ChaineSOIS' constructor does it: the lowest unused index k is paired with the unused j that
+// minimises the imaginary residue of the two quadratics; zeros and poles are paired with the SAME indices (:467-528).  An odd
+// order leaves a first-order section that carries the gain (:530-556), otherwise y *= gain (:558-559,570).
+// (filtre_sois and filtre_sois_canaux)
+struct SectionsSOIS {
+  std::vector<float> coefs;   // nsec rows of (b0, b1, b2, a1, a2), already normalised by a0
+  std::vector<float> rii1;    // (b0, b1, a1) of the first-order section, or empty
+  float gain = 1.0f;          // 1 when rii1 carries it
+};
+inline SectionsSOIS sections_sois(const FRat<cfloat> &f)
+{
+  const Vecteur<cfloat> z = f.numer.roots(), p = f.denom.roots();
+  const entier nz = z.rows(), np = p.rows();
+  if (nz != np) échec("ChaineSOIS: numerator and denominator must have the same degree (nz={}, np={})", (int) nz, (int) np);
+  std::set<entier> libres;
+  for (entier i = 0; i < nz; i++) libres.insert(i);
+  SectionsSOIS s;
+  entier i;
+  for (i = 0; i + 1 < nz; i += 2) {
+    const entier k = *libres.begin();
+    libres.erase(libres.begin());
+    float meilleur = 1e9f, sz = 0, pz = 0, sp = 0, pp = 0;
+    auto choix = libres.begin();
+    for (auto it = libres.begin(); it != libres.end(); ++it) {
+      const entier j = *it;
+      const cfloat sz0 = -(z.data()[j] + z.data()[k]), pz0 = z.data()[j] * z.data()[k];
+      const cfloat sp0 = -(p.data()[j] + p.data()[k]), pp0 = p.data()[j] * p.data()[k];
+      const float err = std::abs(sz0.imag()) + std::abs(pz0.imag()) + std::abs(sp0.imag()) + std::abs(pp0.imag());
+      if (err < meilleur) {
+        choix = it;
+        meilleur = err;
+        sz = sz0.real(); pz = pz0.real(); sp = sp0.real(); pp = pp0.real();
+      }
+    }
+    libres.erase(choix);
+    if (meilleur > 1e-5f) msg("Factorisation SOIS : erreur = {}", meilleur);
+    // section {b0,b1,b2 ; a0,a1,a2} = {1, sz, pz ; 1, sp, pp}, already normalised by a0 (:317-328)
+    for (float v : {1.0f, sz, pz, sp, pp}) s.coefs.push_back(v);
+  }
+  const float g = f.numer.mlt.real() / f.denom.mlt.real();
+  if (i < nz) {
+    const entier id = *libres.begin();
+    s.rii1 = {g, -z.data()[id].real() * g, -p.data()[id].real()};        // (:550-552)
+  } else {
+    s.gain = g;                                                             // (:558-559)
+  }
+  return s;
+}
 
 // ---- several GPUs behind one operator object --------------------------------------------------------
 // A large HOST vector handed to a FIR / SOS / resampler object is cut into contiguous chunks, one per

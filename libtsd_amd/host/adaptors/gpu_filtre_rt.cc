@@ -66,53 +66,13 @@ template <typename T> struct ChaineSOISGpu : FiltreGen<T> {
   int forme = 2, mode = -1;
   ChaineSOISGpu(const FRat<cfloat> &f, RIIStructure structure)
   {
-    const Vecteur<cfloat> z = f.numer.roots(), p = f.denom.roots();
-    const entier nz = z.rows(), np = p.rows();
-    if (nz != np) échec("ChaineSOIS: numerator and denominator must have the same degree (nz={}, np={})", (int) nz, (int) np);
-    std::set<entier> libres;
-    for (entier i = 0; i < nz; i++) libres.insert(i);
-    std::vector<float> coefs;
-    entier i;
-    for (i = 0; i + 1 < nz; i += 2) {
-      const entier k = *libres.begin();
-      libres.erase(libres.begin());
-      float meilleur = 1e9f, sz = 0, pz = 0, sp = 0, pp = 0;
-      auto choix = libres.begin();
-      for (auto it = libres.begin(); it != libres.end(); ++it) {
-        const entier j = *it;
-        const cfloat sz0 = -(z.data()[j] + z.data()[k]), pz0 = z.data()[j] * z.data()[k];
-        const cfloat sp0 = -(p.data()[j] + p.data()[k]), pp0 = p.data()[j] * p.data()[k];
-        const float err = std::abs(sz0.imag()) + std::abs(pz0.imag()) + std::abs(sp0.imag()) + std::abs(pp0.imag());
-        if (err < meilleur) {
-          choix = it;
-          meilleur = err;
-          sz = sz0.real(); pz = pz0.real(); sp = sp0.real(); pp = pp0.real();
-        }
-      }
-      libres.erase(choix);
-      if (meilleur > 1e-5f) msg("Factorisation SOIS : erreur = {}", meilleur);
-      // section {b0,b1,b2 ; a0,a1,a2} = {1, sz, pz ; 1, sp, pp}, already normalised by a0 (:317-328)
-      for (float v : {1.0f, sz, pz, sp, pp}) coefs.push_back(v);
-    }
-    float rii1[3] = {0, 0, 0};
-    bool avec_rii1 = false;
-    float gain = 1.0f;
-    const float g = f.numer.mlt.real() / f.denom.mlt.real();
-    if (i < nz) {
-      const entier id = *libres.begin();
-      rii1[0] = g;                                                          // (:550-552)
-      rii1[1] = -z.data()[id].real() * g;
-      rii1[2] = -p.data()[id].real();
-      avec_rii1 = true;
-    } else {
-      gain = g;                                                             // (:558-559)
-    }
-    if (tsdgpu_sos_create(&h, dtype_of<T>(), coefs.data(), (int) (coefs.size() / 5), gain, avec_rii1 ? rii1 : nullptr,
+    const tsd_amd::SectionsSOIS s = tsd_amd::sections_sois(f);      // the pairing (gpu_commun.hpp)
+    if (tsdgpu_sos_create(&h, dtype_of<T>(), s.coefs.data(), (int) (s.coefs.size() / 5), s.gain, s.rii1.empty() ? nullptr : s.rii1.data(),
                           structure == FormeDirecte2 ? 2 : 1))
       gpu_fail("filtre_sois");
-    coefs_sections = coefs;
-    if (avec_rii1) rii1_v.assign(rii1, rii1 + 3);
-    gain_v = gain;
+    coefs_sections = s.coefs;
+    rii1_v = s.rii1;
+    gain_v = s.gain;
     forme = structure == FormeDirecte2 ? 2 : 1;
   }
   ~ChaineSOISGpu()

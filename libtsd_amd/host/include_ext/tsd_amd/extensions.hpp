@@ -37,6 +37,16 @@ entier filtre_fft_dim(const tsd::fourier::FiltreFFTConfig &config);
 // -1: automatic again), like the environment variable TSD_AMD_SHARDS.
 void fixe_fragments(int n);
 
+// ---- channel banks: C streams of ONE filter in one object (include/tsdgpu.h: tsdgpu_fir_bank / tsdgpu_sos_bank) --------
+// libtsd has no multichannel filter: these are extensions, not stand-ins.  step(x, y): x.rows() == nb_canaux * n, channel after
+// channel (the storage of an n x nb_canaux Tab: Tab::map of a libtsd matrix works), y the same layout; host or resident
+// vectors, in place allowed.  Each channel behaves as its own filtre_rif<Tc,T>(h) / filtre_sois<T>(h, s) object fed the same
+// blocks (the FIR channels bit-identical to a direct-method filtre_rif; up to 12289 taps).
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_canaux(const Vecteur<Tc> &h, entier nb_canaux);
+template <typename T>
+sptr<FiltreGen<T>> filtre_sois_canaux(const FRat<cfloat> &h, entier nb_canaux,
+                                      tsd::filtrage::RIIStructure s = tsd::filtrage::FormeDirecte2);
+
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
 // every adaptor as input, and as output when it already has the size the step produces (resize() to
