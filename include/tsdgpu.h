@@ -282,6 +282,49 @@ int tsdgpu_sos_bank_set_state(tsdgpu_sos_bank *b, int channel, const float *stat
 int tsdgpu_sos_bank_destroy(tsdgpu_sos_bank *b);
 
 /* --------------------------------------------------------------------------------------
+ * Rate-changing channel bank: C streams through ONE integer-rate stage (the kinds of
+ * tsdgpu_poly_kind below: FiltreRIFDecim, FiltreRIFDemiBande, FiltreRIFUps, Decimateur), one
+ * kernel launch per step.  An extension, like the banks above.
+ *  - layout: channel c of a step reads x + c*ldx (n samples) and writes y + c*ldy (*n_out
+ *    samples); ld in samples, 64-bit channel offsets, ldx >= n, ldy >= *n_out.  y_capacity is
+ *    the room of ONE channel's output row (ldy may be larger).  Every channel receives the same
+ *    n, so the bank has ONE phase counter and every channel produces the same number of
+ *    outputs: tsdgpu_polyfir_bank_out_count(b, n), which advances nothing.
+ *  - channel c behaves exactly like its own tsdgpu_polyfir handle of the same kind fed the same
+ *    blocks, bit for bit wherever that handle runs its direct or fused kernel (decimators below
+ *    32 taps, decimators of rate 2 / 4 / 8 up to 64 taps, every half-band up to 64 taps, every
+ *    upsampler, the pick).  Decimators of 32 taps and more outside the direct regime sum oldest
+ *    sample first here, class by class in the single handle: equal to rounding.
+ *  - n == 0 is a no-op; n < R gives no output, the counter and the histories advance.  Host or
+ *    device pointers, strided rows, any 4-B (float) / 8-B (complex) aligned base.  If the x and
+ *    y footprints overlap in any way the step works from a private copy of x.
+ *  - state: channels x tsdgpu_polyfir_bank_history_len() samples, channel-major, oldest first
+ *    (the last inputs of each channel; 0 samples for TSDGPU_POLY_PICK, whose buffer may be
+ *    NULL), host or device, and the phase counter in [0, R).
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): the taps of all branches
+ *    (ntaps for a decimator, ntaps rounded up to a multiple of R for an upsampler) fit 4096
+ *    floats of LDS, and the input span of a workgroup's 256 outputs fits 16000 staged samples
+ *    (a decimator: 257 R + ntaps <= 16000).  These are the limits within which tsdgpu_polyfir
+ *    runs a kernel of its own rather than the FIR-plus-pick composition.  R in [1, 4096].
+ *  - non-finite inputs: as for the single-stream stages, the direct scheme (decimators of rate
+ *    2 / 4 / 8 up to 64 taps, upsamplers of rate 2 / 4 with branches up to 32 taps) multiplies
+ *    its zero-padded taps too, so a NaN / Inf reaches KP - 1 later input samples of ITS OWN
+ *    channel instead of W - 1 (W the taps of a branch, KP = W rounded up to a multiple of 32
+ *    for float and of 16 for complex data); other channels are never touched.
+ * ------------------------------------------------------------------------------------ */
+typedef struct tsdgpu_polyfir_bank tsdgpu_polyfir_bank;
+int tsdgpu_polyfir_bank_create(tsdgpu_polyfir_bank **out, int kind, int data_type, const float *taps_host, int ntaps, int R,
+                               int channels);
+int64_t tsdgpu_polyfir_bank_out_count(tsdgpu_polyfir_bank *b, int64_t n);   /* per channel; advances nothing */
+int tsdgpu_polyfir_bank_step(tsdgpu_polyfir_bank *b, const void *x, int64_t ldx, int64_t n, void *y, int64_t ldy,
+                             int64_t y_capacity, int64_t *n_out, void *stream);
+int tsdgpu_polyfir_bank_reset(tsdgpu_polyfir_bank *b);                      /* histories <- zeros, counter <- 0 */
+int tsdgpu_polyfir_bank_history_len(const tsdgpu_polyfir_bank *b);          /* samples per channel (0 for PICK) */
+int tsdgpu_polyfir_bank_get_state(tsdgpu_polyfir_bank *b, void *hist_dst, int *phase, void *stream);
+int tsdgpu_polyfir_bank_set_state(tsdgpu_polyfir_bank *b, const void *hist_src, int phase, void *stream);
+int tsdgpu_polyfir_bank_destroy(tsdgpu_polyfir_bank *b);
+
+/* --------------------------------------------------------------------------------------
  * Resampler:  AdaptationRythmeSimple<T>::step (factory filtre_itrp) over
  *             InterpolateurRIF::step with the LUT-sinc interpolator itrp_sinc
  *             (src/reechan/ra.cc:13-79; include/tsd/filtrage.hpp:1873-1881;

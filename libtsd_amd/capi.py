@@ -82,6 +82,16 @@ def _declare(L):
     L.tsdgpu_sos_bank_get_state.argtypes = [vp, i32, vp, vp]
     L.tsdgpu_sos_bank_set_state.argtypes = [vp, i32, vp, vp]
     L.tsdgpu_sos_bank_destroy.argtypes = [vp]
+    L.tsdgpu_polyfir_bank_create.argtypes = [C.POINTER(vp), i32, i32, vp, i32, i32, i32]
+    L.tsdgpu_polyfir_bank_out_count.argtypes = [vp, i64]
+    L.tsdgpu_polyfir_bank_out_count.restype = i64
+    L.tsdgpu_polyfir_bank_step.argtypes = [vp, vp, i64, i64, vp, i64, i64, C.POINTER(i64), vp]
+    L.tsdgpu_polyfir_bank_reset.argtypes = [vp]
+    L.tsdgpu_polyfir_bank_history_len.argtypes = [vp]
+    L.tsdgpu_polyfir_bank_history_len.restype = i32
+    L.tsdgpu_polyfir_bank_get_state.argtypes = [vp, vp, C.POINTER(i32), vp]
+    L.tsdgpu_polyfir_bank_set_state.argtypes = [vp, vp, i32, vp]
+    L.tsdgpu_polyfir_bank_destroy.argtypes = [vp]
     L.tsdgpu_resampler_create.argtypes = [C.POINTER(vp), i32, fl, vp, i32, i32]
     L.tsdgpu_resampler_out_count.argtypes = [vp, i64]
     L.tsdgpu_resampler_out_count.restype = i64
@@ -786,6 +796,70 @@ class PolyFir:
         try:
             if self._h:
                 lib().tsdgpu_polyfir_destroy(self._h)
+        except Exception:
+            pass
+
+
+class PolyFirBank:
+    """C channels through ONE integer-rate stage (PolyFir's kinds) in one launch per step (tsdgpu_polyfir_bank): step(x)
+    takes a (C, n) block, row c being channel c, and returns the (C, n_out) outputs; one phase counter for all channels."""
+
+    def __init__(self, kind, data_type, channels, taps=None, R=2):
+        self.kind, self.data_type, self.channels = kind, data_type, int(channels)
+        self._h = C.c_void_p()
+        t = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+        _check(lib().tsdgpu_polyfir_bank_create(C.byref(self._h), kind, data_type, None if t is None else t.ctypes.data,
+                                                0 if t is None else len(t), R, self.channels))
+        self.history_len = lib().tsdgpu_polyfir_bank_history_len(self._h)
+
+    def out_count(self, n):
+        return lib().tsdgpu_polyfir_bank_out_count(self._h, int(n))
+
+    def step(self, x, y=None, stream=None):
+        """x: (C, n) numpy array (host) or torch tensor (host or device), float32 / complex64, rows may be strided.
+        y: (C, m) with m >= out_count(n), of x's kind (default: a new packed one); returns its (C, n_out) view."""
+        assert _dtype_code(x) == self.data_type, "input dtype does not match the bank's data type"
+        n = int(x.shape[1])
+        nout = self.out_count(n)
+        if y is None:
+            y = np.empty((self.channels, nout), x.dtype) if isinstance(x, np.ndarray) else x.new_empty((self.channels, nout))
+        assert _dtype_code(y) == self.data_type, "output dtype does not match the bank's data type"
+        px, ldx = _ptr2d(x, self.channels)
+        py, ldy = _ptr2d(y, self.channels)
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_polyfir_bank_step(self._h, px, ldx, n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
+        return y[:, : got.value]
+
+    def reset(self):
+        _check(lib().tsdgpu_polyfir_bank_reset(self._h))
+
+    def _hist_dtype(self):
+        return np.complex64 if self.data_type == C64 else np.float32
+
+    def get_state(self, dst=None, stream=None):
+        """((C, history_len) samples, oldest first per channel; phase counter).  dst: packed numpy array or torch tensor."""
+        if dst is None:
+            dst = np.zeros((self.channels, self.history_len), self._hist_dtype())
+        assert tuple(dst.shape) == (self.channels, self.history_len) and _dtype_code(dst) == self.data_type
+        phase = C.c_int(0)
+        _check(lib().tsdgpu_polyfir_bank_get_state(self._h, _ptr(dst) if self.history_len else None, C.byref(phase),
+                                                   _stream_of(dst, stream)))
+        return dst, phase.value
+
+    def set_state(self, hist, phase, stream=None):
+        if self.history_len:
+            assert tuple(hist.shape) == (self.channels, self.history_len) and _dtype_code(hist) == self.data_type
+        _check(lib().tsdgpu_polyfir_bank_set_state(self._h, _ptr(hist) if self.history_len else None, int(phase),
+                                                   _stream_of(hist, stream) if self.history_len else stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_polyfir_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

@@ -9,6 +9,7 @@
 // rates or tap counts that do not fit its LDS tile fall back to compositions of the FIR
 // kernels of fir.hip / ols.hip with small permutation kernels on device scratch.
 #include "common.hpp"
+#include "poly_internal.hpp"
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -40,11 +41,7 @@ __global__ void interleave_kernel(const T *__restrict__ z, T *__restrict__ y, in
 // span of its PF_TO outputs in LDS with coalesced loads; every thread then evaluates
 // PF_TO/256 outputs from LDS (taps in LDS too).  Algorithmic bytes per input sample:
 // 8 + 8/R (decimate) or 8 + 8 R (upsample) for complex data.
-#ifndef PF_SPAN_TARGET
-#define PF_SPAN_TARGET 2048
-#endif
-constexpr int PF_TO = 2048;          // outputs per workgroup (fewer when the decimation rate makes their input span too long)
-constexpr int PF_MAX_SPAN = 16000;   // staged input samples per workgroup (129 KiB of complex data with the padding)
+// (PF_TO outputs per workgroup, PF_MAX_SPAN staged samples: poly_internal.hpp)
 __device__ __forceinline__ float pf_mac(float acc, float g, float x) { return fmaf(g, x, acc); }
 __device__ __forceinline__ float2 pf_mac(float2 acc, float g, float2 x) { return make_float2(fmaf(g, x.x, acc.x), fmaf(g, x.y, acc.y)); }
 __device__ __forceinline__ float pf_zero(float) { return 0.f; }
@@ -689,11 +686,9 @@ int launch_pick(const void *x, void *y, int64_t start, int R, int64_t nout, hipS
 // the fused kernel serves a stage when its taps and the input span of PF_TO outputs fit in LDS
 int fused_setup(tsdgpu_polyfir *p, const std::vector<float> &g, int NPH, int W, int stride)
 {
-  // outputs per workgroup: as many as keep the staged input span within PF_MAX_SPAN samples
-  // ... and preferably within ~PF_SPAN_TARGET samples (17 KiB: several workgroups per CU overlap their load and compute phases)
-  int64_t to = std::min<int64_t>(PF_TO, ((int64_t) (PF_MAX_SPAN - W) / stride - 1) * NPH);
-  to = std::min<int64_t>(to, std::max<int64_t>(256, (int64_t) (PF_SPAN_TARGET / stride) * NPH));
-  if (dev_switch("POLY_COMPOSED") || to < 256 || (size_t) NPH * W > 4096 || W < 1) return TSDGPU_OK;
+  // outputs per workgroup and the limits of the kernel: poly_internal.hpp (the channel bank plans with the same)
+  const int64_t to = poly_fused_outputs(NPH, W, stride);
+  if (dev_switch("POLY_COMPOSED") || !poly_fused_serves(NPH, W, stride)) return TSDGPU_OK;
   p->TO = (int) (to / 256 * 256);
   p->NPH = NPH;
   p->W = W;
@@ -702,19 +697,13 @@ int fused_setup(tsdgpu_polyfir *p, const std::vector<float> &g, int NPH, int W, 
   // allocations, a copy, two memsets and a synchronisation before: a third of a one-shot rééchan(x, 4))
   const size_t hb = ((size_t) p->HW * dtype_size(p->data_type) + 15) / 16 * 16, gb = (g.size() * sizeof(float) + 15) / 16 * 16;
   // decimators of rate 2 / 4 / 8 up to 64 taps: the reversed, padded taps of decim_direct_kernel behind the histories
-  const int RSd = p->data_type == TSDGPU_F32 ? 16 : 8;
   // ... and upsamplers of rate 2 / 4 with branches of up to 32 taps (ups_direct_kernel): one such row per branch
-  const bool updir = stride == 1 && (NPH == 2 || NPH == 4) && W <= 32 && dev_switch("POLY_NO_DIRECT") == nullptr;
-  const bool direct = (NPH == 1 && (stride == 2 || stride == 4 || stride == 8) && W <= 64 && dev_switch("POLY_NO_DIRECT") == nullptr) || updir;
-  p->KPd = direct ? (int) (cdiv(W, 2 * RSd) * 2 * RSd) : 0;
+  const bool direct = poly_direct_regime(NPH, W, stride) && dev_switch("POLY_NO_DIRECT") == nullptr;
+  p->KPd = direct ? poly_direct_kp(W, p->data_type) : 0;
   const size_t rb = (size_t) p->KPd * NPH * sizeof(float);
   std::vector<char> image(gb + 2 * hb + rb, 0);
   std::memcpy(image.data(), g.data(), g.size() * sizeof(float));
-  if (direct) {
-    float *hr = reinterpret_cast<float *>(image.data() + gb + 2 * hb);
-    for (int i = 0; i < NPH; i++)
-      for (int k = 0; k < W; k++) hr[(size_t) i * p->KPd + p->KPd - 1 - k] = g[(size_t) i * W + k];   // hrev[j] = g[KP - 1 - j]: g[0] meets the newest sample
-  }
+  if (direct) poly_direct_rows(g, NPH, W, p->KPd, reinterpret_cast<float *>(image.data() + gb + 2 * hb));   // hrev[j] = g[KP - 1 - j]
   if (hipMalloc((void **) &p->d_g, image.size()) != hipSuccess)
     return set_err(TSDGPU_ERR_HIP, "polyfir_create: hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
   p->d_hist[0] = (char *) p->d_g + gb;
@@ -822,15 +811,8 @@ int tsdgpu_polyfir_create(tsdgpu_polyfir **out, int kind, int data_type, const f
   p->K = ntaps;
   int rc = TSDGPU_OK;
   if (kind == TSDGPU_POLY_DECIM || kind == TSDGPU_POLY_HALFBAND) {
-    // window is correlated with the taps in forward order (polyphase.cc:223-229) == an FIR
-    // with the taps reversed; half-band keeps the even taps and forces 0.5 on the centre sample
-    std::vector<float> h((size_t) ntaps);
-    for (int k = 0; k < ntaps; k++) {
-      const int i = ntaps - 1 - k;
-      float c = taps_host[i];
-      if (kind == TSDGPU_POLY_HALFBAND) c = ((i & 1) == 0 ? c : 0.f) + (i == ntaps / 2 ? 0.5f : 0.f);
-      h[k] = c;
-    }
+    // the taps reversed; the half-band's even taps and 0.5 on the centre sample (poly_tap_image)
+    const std::vector<float> h = poly_tap_image(kind, taps_host, ntaps, R).g;
     // (the composition -- a full-rate FIR, then the pick -- only where the fused kernel does not serve: building its
     // handle costs a one-shot rééchan() 30 us per stage)
     rc = fused_setup(p, h, 1, ntaps, R);
@@ -840,15 +822,10 @@ int tsdgpu_polyfir_create(tsdgpu_polyfir **out, int kind, int data_type, const f
       if (!rc) p->fir.push_back(f);
     }
   } else if (kind == TSDGPU_POLY_UPS) {
-    // coefs = c * R, zero-padded to a multiple of R (polyphase.cc:259-270); phase i correlates
-    // the K/R-sample window with coefs[(R-1-i) + j*R]
-    std::vector<float> c((size_t) ntaps);
-    for (int i = 0; i < ntaps; i++) c[i] = taps_host[i] * (float) R;
-    while (c.size() % (size_t) R) c.push_back(0.f);
-    const int W = (int) c.size() / R;
-    std::vector<float> gall;
-    for (int i = 0; i < R; i++)
-      for (int k = 0; k < W; k++) gall.push_back(c[(size_t) (R - 1 - i) + (size_t) (W - 1 - k) * R]);
+    // coefs = c * R, zero-padded to a multiple of R, split in R branches (poly_tap_image)
+    const PolyImage im = poly_tap_image(kind, taps_host, ntaps, R);
+    const int W = im.W;
+    const std::vector<float> &gall = im.g;
     rc = fused_setup(p, gall, R, W, 1);
     for (int i = 0; i < R && !rc && !p->fused; i++) {      // the composition (R branch FIRs + interleave) only without the fused kernel
       tsdgpu_fir *f = nullptr;

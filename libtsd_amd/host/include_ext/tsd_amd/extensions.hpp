@@ -47,6 +47,16 @@ template <typename T>
 sptr<FiltreGen<T>> filtre_sois_canaux(const FRat<cfloat> &h, entier nb_canaux,
                                       tsd::filtrage::RIIStructure s = tsd::filtrage::FormeDirecte2);
 
+// ---- rate-changing channel banks: C streams through ONE integer-rate stage (include/tsdgpu.h: tsdgpu_polyfir_bank) ------
+// The same extension for filtre_rif_decim / filtre_rif_demi_bande / filtre_rif_ups / decimateur.  step(x, y): x.rows() ==
+// nb_canaux * n, channel after channel; y is resized to nb_canaux * n_out, same layout (all channels share one phase counter,
+// hence one n_out); host or resident vectors.  Each channel behaves as its own single-stream object fed the same blocks.
+// Served: the taps of all branches within 4096 floats and 257 R + K <= 16000 for a decimator (tsdgpu.h); else the factory fails.
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_decim_canaux(const Vecteur<Tc> &h, entier R, entier nb_canaux);
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_demi_bande_canaux(const Vecteur<Tc> &h, entier nb_canaux);
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_ups_canaux(const Vecteur<Tc> &h, entier R, entier nb_canaux);
+template <typename T> sptr<FiltreGen<T>> decimateur_canaux(entier R, entier nb_canaux);
+
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
 // every adaptor as input, and as output when it already has the size the step produces (resize() to
