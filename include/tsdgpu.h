@@ -258,11 +258,27 @@ int tsdgpu_sos_destroy(tsdgpu_sos *s);
  *    streams as everywhere in this header.  The fast path takes 16-B aligned channel bases
  *    (aligned x / y, ld * sizeof(sample) % 16 == 0); other layouts are served as well.
  *  - create: the argument checks of tsdgpu_fir_create / tsdgpu_sos_create, plus channels >= 1
- *    (TSDGPU_ERR_INVALID).  A FIR bank always runs the direct scheme: more than 12289 taps is
- *    TSDGPU_ERR_UNSUPPORTED.  Each channel's output is bit-identical to a TSDGPU_FIR_DIRECT handle.
+ *    (TSDGPU_ERR_INVALID); more than 12289 taps is TSDGPU_ERR_UNSUPPORTED for a FIR bank.
+ *  - FIR bank methods (tsdgpu_fir_bank_create_method; an invalid method is TSDGPU_ERR_INVALID):
+ *    TSDGPU_FIR_DIRECT, which is what tsdgpu_fir_bank_create makes: the direct scheme, each
+ *    channel's output bit-identical to a TSDGPU_FIR_DIRECT handle.
+ *    TSDGPU_FIR_OVERLAP_SAVE: overlap-save on 1024-point blocks, one launch per step, for 2 to
+ *    961 taps; outside that range the bank runs the direct scheme, as a single handle does, and
+ *    says so through tsdgpu_fir_bank_method_used.  Each channel's output is within 1e-5 of the
+ *    peak of the reference, aligned as DIRECT's: no delay, as for the single handle.  Channels
+ *    never share a transform: one non-finite input sample makes the outputs of its own blocks
+ *    (at most 2048 samples on either side) non-finite and nothing outside its channel.
+ *    TSDGPU_FIR_AUTO: chosen per step from the tap count, the types and n (short channels and
+ *    short filters take the direct scheme); both schemes share the channels' histories, so
+ *    the stream continues whichever scheme a step takes, within the overlap-save promise.
+ *    The history exchange is the same for every method: channels x (ntaps-1) samples.
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_fir_bank tsdgpu_fir_bank;
 int tsdgpu_fir_bank_create(tsdgpu_fir_bank **out, int data_type, int tap_type, const void *taps_host, int ntaps, int channels);
+int tsdgpu_fir_bank_create_method(tsdgpu_fir_bank **out, int data_type, int tap_type, const void *taps_host,
+                                  int ntaps, int channels, int method /* tsdgpu_fir_method */);
+/* the scheme of the LAST step, TSDGPU_FIR_DIRECT or TSDGPU_FIR_OVERLAP_SAVE; before any step: what a step of n >= 1024 would take */
+int tsdgpu_fir_bank_method_used(const tsdgpu_fir_bank *b);
 int tsdgpu_fir_bank_step(tsdgpu_fir_bank *b, const void *x, int64_t ldx, void *y, int64_t ldy, int64_t n, void *stream);
 int tsdgpu_fir_bank_reset(tsdgpu_fir_bank *b);           /* every history <- zeros */
 /* dst / src: channels x (ntaps-1) samples, channel-major, oldest first (tsdgpu_fir_get_history per channel); host or device */

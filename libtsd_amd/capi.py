@@ -71,6 +71,8 @@ def _declare(L):
     L.tsdgpu_sos_halo.restype = i64
     L.tsdgpu_sos_destroy.argtypes = [vp]
     L.tsdgpu_fir_bank_create.argtypes = [C.POINTER(vp), i32, i32, vp, i32, i32]
+    L.tsdgpu_fir_bank_create_method.argtypes = [C.POINTER(vp), i32, i32, vp, i32, i32, i32]
+    L.tsdgpu_fir_bank_method_used.argtypes = [vp]
     L.tsdgpu_fir_bank_step.argtypes = [vp, vp, i64, vp, i64, i64, vp]
     L.tsdgpu_fir_bank_reset.argtypes = [vp]
     L.tsdgpu_fir_bank_get_history.argtypes = [vp, vp, vp]
@@ -596,15 +598,22 @@ def _bank_out(x, y):
 
 class FirBank:
     """C channels of filtre_rif<Tc,T>(h) in one launch per step (tsdgpu_fir_bank): step(x) filters a (C, n) block, row c
-    being channel c; every channel bit-identical to its own Fir(h, data_type, FIR_DIRECT) fed the same blocks."""
+    being channel c.  method FIR_DIRECT (the default): every channel bit-identical to its own Fir(h, data_type, FIR_DIRECT)
+    fed the same blocks; FIR_OVERLAP_SAVE (2 .. 961 taps) / FIR_AUTO (chosen per step): within 1e-5 of the peak."""
 
-    def __init__(self, taps, data_type, channels):
+    def __init__(self, taps, data_type, channels, method=FIR_DIRECT):
         taps = np.ascontiguousarray(taps)
         tt = C64 if np.iscomplexobj(taps) else F32
         taps = taps.astype(np.complex64 if tt == C64 else np.float32)
         self.K, self.data_type, self.channels = len(taps), data_type, int(channels)
         self._h = C.c_void_p()
-        _check(lib().tsdgpu_fir_bank_create(C.byref(self._h), data_type, tt, taps.ctypes.data, len(taps), self.channels))
+        _check(lib().tsdgpu_fir_bank_create_method(C.byref(self._h), data_type, tt, taps.ctypes.data, len(taps), self.channels,
+                                                   int(method)))
+
+    @property
+    def method_used(self):
+        """the scheme of the last step (FIR_DIRECT or FIR_OVERLAP_SAVE); before any step, what a step of n >= 1024 would take"""
+        return lib().tsdgpu_fir_bank_method_used(self._h)
 
     def step(self, x, y=None, stream=None):
         """x: (C, n) numpy array (host) or torch tensor (host or device), float32 / complex64, rows may be strided."""

@@ -11,6 +11,8 @@
 // (fir_direct_kernel keeps 16-B accesses for interior tiles only: at n = 4096 every one of its tiles is an edge tile.)
 // The multiply-adds are the direct kernel's, in its order: a channel's output is bit-identical to a TSDGPU_FIR_DIRECT handle.
 // The channel's last tile also writes the channel's new history: one launch per step.
+// Created with TSDGPU_FIR_OVERLAP_SAVE or TSDGPU_FIR_AUTO the bank also owns the 1024-point overlap-save plan (ols_bank.hip) and
+// chooses between the two schemes per step; both read and write the same C x HL history rows.
 //
 // SOS bank: sos_kernel's block-parallel cascade (sos.hip) with a channel grid dimension.  Each channel has its own state slot
 // (the single-stream record layout: seeded flag, then the memories), and the wave that owns a channel's last chunk also runs
@@ -24,8 +26,16 @@
 #include <algorithm>
 
 struct tsdgpu_fir_bank {
-  tsdgpu_fir *proto = nullptr;   // a direct handle: reversed padded taps (d_hrev), KP, HL; its own history serves no channel
+  // a direct handle: reversed padded taps (d_hrev), KP; its own history serves no channel.  With the overlap-save scheme it also
+  // carries the 1024-point plan's tables (d_H, ols_L: ols_bank.hip)
+  tsdgpu_fir *proto = nullptr;
   int64_t C = 0;
+  int method = TSDGPU_FIR_DIRECT;       // as requested at creation
+  bool ols = false;                     // the overlap-save plan exists (2 <= K <= 961 and the method asks for it)
+  int ols_grid = 0;                     // its persistent grid (resident waves)
+  int last = TSDGPU_FIR_DIRECT;         // the scheme of the last step
+  bool stepped = false;
+  int HL = 0;                           // samples per history row: both schemes read the row's END, so the longer need serves both
   void *hist[2] = {nullptr, nullptr};   // C rows of HL samples each (double-buffered), newest last
   int cur = 0;
   int ymax = 0;                  // the grid's y limit (channels per launch)
@@ -210,10 +220,10 @@ int fir_bank_launch(tsdgpu_fir_bank *b, const void *x, int64_t ldx, void *y, int
     const unsigned cy = (unsigned) std::min<int64_t>(b->ymax, b->C - c0);
     if (al)
       hipLaunchKernelGGL((fir_bank_kernel<T, TC, R, THREADS, true>), dim3((unsigned) tiles, cy), dim3(THREADS), lds, st, (const T *) x, ldx,
-                         (T *) y, ldy, (const TC *) f->d_hrev, KP, n, oldh, newh, f->HL, c0);
+                         (T *) y, ldy, (const TC *) f->d_hrev, KP, n, oldh, newh, b->HL, c0);
     else
       hipLaunchKernelGGL((fir_bank_kernel<T, TC, R, THREADS, false>), dim3((unsigned) tiles, cy), dim3(THREADS), lds, st, (const T *) x, ldx,
-                         (T *) y, ldy, (const TC *) f->d_hrev, KP, n, oldh, newh, f->HL, c0);
+                         (T *) y, ldy, (const TC *) f->d_hrev, KP, n, oldh, newh, b->HL, c0);
     TSD_HIP(hipGetLastError());
   }
   return TSDGPU_OK;
@@ -441,17 +451,28 @@ extern "C" {
 // ------------------------------------------------------------------ FIR bank
 int tsdgpu_fir_bank_create(tsdgpu_fir_bank **out, int data_type, int tap_type, const void *taps_host, int ntaps, int channels)
 {
+  return tsdgpu_fir_bank_create_method(out, data_type, tap_type, taps_host, ntaps, channels, TSDGPU_FIR_DIRECT);
+}
+
+int tsdgpu_fir_bank_create_method(tsdgpu_fir_bank **out, int data_type, int tap_type, const void *taps_host, int ntaps, int channels,
+                                  int method)
+{
   TSD_CHECK(out != nullptr, "fir_bank_create: out is NULL");
   *out = nullptr;
   TSD_CHECK(channels >= 1, "fir_bank_create: channels = %d, need at least one", channels);
+  TSD_CHECK(method >= TSDGPU_FIR_AUTO && method <= TSDGPU_FIR_OVERLAP_SAVE, "fir_bank_create: bad method %d", method);
   if (ntaps > 12289)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "fir_bank_create: %d taps, the bank's direct scheme serves up to 12289", ntaps);
   tsdgpu_fir_bank *b = new tsdgpu_fir_bank();
   b->C = channels;
+  b->method = method;
   int rc = tsdgpu_fir_create(&b->proto, data_type, tap_type, taps_host, ntaps, TSDGPU_FIR_DIRECT);
   if (!rc) rc = grid_y_limit(&b->ymax);
+  // the overlap-save plan inside its envelope (2 .. 961 taps); outside it the bank runs the direct scheme, as a single handle does
+  if (!rc && method != TSDGPU_FIR_DIRECT) rc = ols_bank_plan(b->proto, &b->ols, &b->ols_grid);
   if (!rc) {
-    const size_t hb = (size_t) channels * (size_t) b->proto->HL * dtype_size(data_type);
+    b->HL = b->ols ? std::max(b->proto->HL, ols_bank_overlap(b->proto)) : b->proto->HL;
+    const size_t hb = (size_t) channels * (size_t) b->HL * dtype_size(data_type);
     if (hipMalloc(&b->hist[0], 2 * hb) != hipSuccess) {
       rc = set_err(TSDGPU_ERR_ALLOC, "fir_bank_create: hipMalloc of %zu bytes failed: %s", 2 * hb, hipGetErrorString(hipGetLastError()));
     } else {
@@ -485,18 +506,30 @@ int tsdgpu_fir_bank_step(tsdgpu_fir_bank *b, const void *x, int64_t ldx, void *y
   bool staged;
   if ((rc = bank_stage_in(x, ldx, n, b->C, sz, in_place, n, b->in_stage, st, &dx, &dldx))) return rc;
   if ((rc = bank_stage_out(y, ldy, b->C, sz, false, n, b->out_stage, &dy, &dldy, &staged))) return rc;
-  if (b->proto->data_type == TSDGPU_F32) rc = fir_bank_launch<float, float, 16>(b, dx, dldx, dy, dldy, n, st);
+  // the scheme of this step: AUTO decides per step (the channel length matters as much as the tap count)
+  const bool ols = b->ols && (b->method == TSDGPU_FIR_OVERLAP_SAVE || ols_bank_preferred(b->proto, n));
+  if (ols) rc = ols_bank_launch(b->proto, b->ols_grid, b->C, dx, dldx, dy, dldy, n, b->hist[b->cur], b->hist[b->cur ^ 1], b->HL, st);
+  else if (b->proto->data_type == TSDGPU_F32) rc = fir_bank_launch<float, float, 16>(b, dx, dldx, dy, dldy, n, st);
   else if (b->proto->tap_type == TSDGPU_F32) rc = fir_bank_launch<float2, float, 8>(b, dx, dldx, dy, dldy, n, st);
   else rc = fir_bank_launch<float2, float2, 8>(b, dx, dldx, dy, dldy, n, st);
   if (rc) return rc;
   b->cur ^= 1;
+  b->last = ols ? TSDGPU_FIR_OVERLAP_SAVE : TSDGPU_FIR_DIRECT;
+  b->stepped = true;
   return bank_finish_out(y, ldy, n, b->C, sz, dy, dldy, staged, st);
+}
+
+int tsdgpu_fir_bank_method_used(const tsdgpu_fir_bank *b)
+{
+  if (!b) return -1;
+  if (b->stepped) return b->last;
+  return b->ols && (b->method == TSDGPU_FIR_OVERLAP_SAVE || ols_bank_preferred(b->proto, 1024)) ? TSDGPU_FIR_OVERLAP_SAVE : TSDGPU_FIR_DIRECT;
 }
 
 int tsdgpu_fir_bank_reset(tsdgpu_fir_bank *b)
 {
   TSD_CHECK(b != nullptr, "fir_bank_reset: NULL handle");
-  TSD_HIP(hipMemset(b->hist[b->cur], 0, (size_t) b->C * (size_t) b->proto->HL * dtype_size(b->proto->data_type)));
+  TSD_HIP(hipMemset(b->hist[b->cur], 0, (size_t) b->C * (size_t) b->HL * dtype_size(b->proto->data_type)));
   TSD_HIP(hipStreamSynchronize(nullptr));      // see tsdgpu_sos_reset
   return TSDGPU_OK;
 }
@@ -505,7 +538,7 @@ int tsdgpu_fir_bank_reset(tsdgpu_fir_bank *b)
 int tsdgpu_fir_bank_get_history(tsdgpu_fir_bank *b, void *dst, void *stream)
 {
   TSD_CHECK(b != nullptr && dst != nullptr, "fir_bank_get_history: NULL argument");
-  const int K1 = b->proto->K - 1, HL = b->proto->HL;
+  const int K1 = b->proto->K - 1, HL = b->HL;
   if (K1 < 1) return TSDGPU_OK;
   hipStream_t st = (hipStream_t) stream;
   const size_t sz = dtype_size(b->proto->data_type);
@@ -520,7 +553,7 @@ int tsdgpu_fir_bank_get_history(tsdgpu_fir_bank *b, void *dst, void *stream)
 int tsdgpu_fir_bank_set_history(tsdgpu_fir_bank *b, const void *src, void *stream)
 {
   TSD_CHECK(b != nullptr && src != nullptr, "fir_bank_set_history: NULL argument");
-  const int K1 = b->proto->K - 1, HL = b->proto->HL;
+  const int K1 = b->proto->K - 1, HL = b->HL;
   if (K1 < 1) return TSDGPU_OK;
   hipStream_t st = (hipStream_t) stream;
   const size_t sz = dtype_size(b->proto->data_type);

@@ -69,3 +69,13 @@ inline int bank_finish_out(void *y, int64_t ldy, int64_t n, int64_t C, size_t sz
 }
 
 }  // namespace tsdgpu
+
+// the overlap-save path of the FIR bank (ols_bank.hip)
+struct tsdgpu_fir;
+namespace tsdgpu {
+int ols_bank_plan(tsdgpu_fir *proto, bool *served, int *grid);
+int ols_bank_overlap(const tsdgpu_fir *proto);               // samples of a block that overlap the one before: whole 64-sample rows
+bool ols_bank_preferred(const tsdgpu_fir *proto, int64_t n);  // the AUTO rule of a step of n samples per channel
+int ols_bank_launch(const tsdgpu_fir *proto, int grid, int64_t C, const void *x, int64_t ldx, void *y, int64_t ldy, int64_t n,
+                    const void *hist_old, void *hist_new, int HL, hipStream_t st);
+}  // namespace tsdgpu

@@ -25,6 +25,7 @@ struct tsdgpu_fir {
   unsigned *d_ctr = nullptr;   // work counters of the dynamic block hand-out (ols.hip: OlsDyn), behind d_H
   int ctr_nc = 0;              // how many of them the launches so far have used
   unsigned ctr_base = 0;       // their common value before the next launch (every launch advances all of them alike)
+  bool ols_short_only = false;   // never the long-filter plan: the FIR bank's prototype keeps the 1024-point tables up to 961 taps (ols_bank.hip)
   bool ols_long = false;    // long-filter plan (ols_long.hip): N = 4096..16384, H in natural order + W_N table
   // partitioned plan for more than 12289 taps: the taps cut in segments of part_S, one child filter per
   // segment (each on the long-filter overlap-save plan), y = sum_p child_p(x delayed by p * part_S)

@@ -107,7 +107,7 @@ void host_fft(std::vector<std::complex<double>> &a)
 bool ols_long_supported(const tsdgpu_fir *f)
 {
   static const int KMIN = dev_switch("OLS_LONG_MIN") ? atoi(dev_switch("OLS_LONG_MIN")) : 514;
-  return f->K >= KMIN && f->K <= 12289;
+  return !f->ols_short_only && f->K >= KMIN && f->K <= 12289;
 }
 
 int ols_long_plan_create(tsdgpu_fir *f)

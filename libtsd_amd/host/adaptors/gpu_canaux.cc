@@ -20,11 +20,12 @@ template <typename V> entier bloc_canal(const V &x, entier nb_canaux, const char
 template <typename T, typename Tc> struct FiltreRIFCanauxGpu : FiltreGen<T> {
   tsdgpu_fir_bank *h = nullptr;
   entier C;
-  FiltreRIFCanauxGpu(const Vecteur<Tc> &c, entier nb_canaux) : C(nb_canaux)
+  FiltreRIFCanauxGpu(const Vecteur<Tc> &c, entier nb_canaux, int méthode = TSDGPU_FIR_DIRECT) : C(nb_canaux)
   {
     if (c.rows() <= 0) échec("filtre_rif_canaux: K > 0 required (K = {})", (int) c.rows());
     if (nb_canaux < 1) échec("filtre_rif_canaux: nb_canaux >= 1 required ({})", (int) nb_canaux);
-    if (tsdgpu_fir_bank_create(&h, dtype_of<T>(), dtype_of<Tc>(), c.data(), c.rows(), (int) nb_canaux)) gpu_fail("filtre_rif_canaux");
+    if (tsdgpu_fir_bank_create_method(&h, dtype_of<T>(), dtype_of<Tc>(), c.data(), c.rows(), (int) nb_canaux, méthode))
+      gpu_fail("filtre_rif_canaux");
   }
   ~FiltreRIFCanauxGpu() { tsdgpu_fir_bank_destroy(h); }
   void step(const Vecteur<T> &x, Vecteur<T> &y)
@@ -62,6 +63,14 @@ template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_canaux(const Ve
 template sptr<FiltreGen<float>> filtre_rif_canaux<float, float>(const Vecteur<float> &, entier);
 template sptr<FiltreGen<cfloat>> filtre_rif_canaux<float, cfloat>(const Vecteur<float> &, entier);
 template sptr<FiltreGen<cfloat>> filtre_rif_canaux<cfloat, cfloat>(const Vecteur<cfloat> &, entier);
+
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_canaux(const Vecteur<Tc> &h, entier nb_canaux, MethodeRIF méthode)
+{
+  return std::make_shared<FiltreRIFCanauxGpu<T, Tc>>(h, nb_canaux, (int) méthode);
+}
+template sptr<FiltreGen<float>> filtre_rif_canaux<float, float>(const Vecteur<float> &, entier, MethodeRIF);
+template sptr<FiltreGen<cfloat>> filtre_rif_canaux<float, cfloat>(const Vecteur<float> &, entier, MethodeRIF);
+template sptr<FiltreGen<cfloat>> filtre_rif_canaux<cfloat, cfloat>(const Vecteur<cfloat> &, entier, MethodeRIF);
 
 template <typename T> sptr<FiltreGen<T>> filtre_sois_canaux(const FRat<cfloat> &h, entier nb_canaux, tsd::filtrage::RIIStructure s)
 {

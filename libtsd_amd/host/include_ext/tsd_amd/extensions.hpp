@@ -43,6 +43,12 @@ void fixe_fragments(int n);
 // vectors, in place allowed.  Each channel behaves as its own filtre_rif<Tc,T>(h) / filtre_sois<T>(h, s) object fed the same
 // blocks (the FIR channels bit-identical to a direct-method filtre_rif; up to 12289 taps).
 template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_canaux(const Vecteur<Tc> &h, entier nb_canaux);
+// The same bank on a chosen scheme: RIF_DIRECTE is the two-argument form; RIF_OLS filters by overlap-save on 1024-point blocks
+// (2 .. 961 taps; outside that range the direct scheme serves the request), each channel within 1e-5 of the reference's peak,
+// aligned as the direct bank, a non-finite sample reaching its own blocks of its own channel only; RIF_AUTO chooses per step
+// from the tap count and the block length (tsdgpu.h: tsdgpu_fir_bank_create_method).
+enum MethodeRIF { RIF_AUTO = 0, RIF_DIRECTE = 1, RIF_OLS = 2 };      // (the values of tsdgpu_fir_method)
+template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_canaux(const Vecteur<Tc> &h, entier nb_canaux, MethodeRIF méthode);
 template <typename T>
 sptr<FiltreGen<T>> filtre_sois_canaux(const FRat<cfloat> &h, entier nb_canaux,
                                       tsd::filtrage::RIIStructure s = tsd::filtrage::FormeDirecte2);
