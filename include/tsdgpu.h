@@ -341,6 +341,46 @@ int tsdgpu_polyfir_bank_set_state(tsdgpu_polyfir_bank *b, const void *hist_src, 
 int tsdgpu_polyfir_bank_destroy(tsdgpu_polyfir_bank *b);
 
 /* --------------------------------------------------------------------------------------
+ * Polyphase channelizer: ONE wideband complex64 stream into `channels` = M channel rows (the
+ * maximally decimated analysis bank), one kernel launch per step.  An extension, like the
+ * banks above: it makes the (C, n) block they read.  With a real prototype h of K taps,
+ * samples counted from creation or reset and zeros before sample 0, output frame m is
+ *     y_c[m] = sum_{k<K} h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M),  n_m = m M + M - 1:
+ * channel c (centre c/M of the input rate) shifted to DC, filtered with h, every M-th sample
+ * kept.  No normalisation: a tone at a channel's centre comes out with gain sum(h).
+ *  - layout: a step takes n = F*M samples of x (F whole frames) and writes F outputs to each
+ *    row y + c*ldy, c < M (ld in samples): a channelizer output feeds a bank of C = M channels
+ *    without a copy.  y_capacity is the room of ONE row.  *n_out = F.
+ *  - n % M != 0, y_capacity < F, ldy < F and ANY overlap of the x and y footprints are
+ *    TSDGPU_ERR_INVALID and advance nothing (there is no in-place form: the layouts differ).
+ *    n == 0 is a no-op.
+ *  - host or device pointers; rows and x need only 8-B alignment (16-B aligned rows -- aligned
+ *    base, even ldy -- take wider stores; the bits are the same).
+ *  - state: the last tsdgpu_channelizer_history_len() = (P - 1) M input samples, oldest first,
+ *    P = ceil(K / M); host or device; 0 samples for K <= M, whose buffer may be NULL.  A state
+ *    moved to a fresh handle continues the stream bit for bit.
+ *  - a stream gives the same bits in one step or in many steps of any frame counts.
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [8, 1024], K <= 16 M.  M < 1, K < 1 and NULL pointers are TSDGPU_ERR_INVALID.
+ *  - error bound: the channels of a frame share one M-point transform, unlike the banks, so
+ *    the bound is 1e-5 of the peak over ALL channels of the step, not per channel: a weak
+ *    channel next to a strong one carries the strong one's rounding.
+ *  - non-finite inputs: a NaN / Inf in input frame f makes ALL channels of output frames
+ *    f .. f + P - 1 non-finite (the shared transform; the zero-padded taps of the last branch are
+ *    multiplied too) and nothing else: every other output has the bits of the clean run.
+ * ------------------------------------------------------------------------------------ */
+typedef struct tsdgpu_channelizer tsdgpu_channelizer;
+int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps);
+int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n);   /* n / channels; advances nothing */
+int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, void *y, int64_t ldy, int64_t y_capacity,
+                            int64_t *n_out, void *stream);
+int tsdgpu_channelizer_reset(tsdgpu_channelizer *c);                            /* history <- zeros */
+int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c);                /* (P - 1) * channels */
+int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *stream);
+int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, void *stream);
+int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);
+
+/* --------------------------------------------------------------------------------------
  * Resampler:  AdaptationRythmeSimple<T>::step (factory filtre_itrp) over
  *             InterpolateurRIF::step with the LUT-sinc interpolator itrp_sinc
  *             (src/reechan/ra.cc:13-79; include/tsd/filtrage.hpp:1873-1881;

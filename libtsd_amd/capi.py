@@ -94,6 +94,16 @@ def _declare(L):
     L.tsdgpu_polyfir_bank_get_state.argtypes = [vp, vp, C.POINTER(i32), vp]
     L.tsdgpu_polyfir_bank_set_state.argtypes = [vp, vp, i32, vp]
     L.tsdgpu_polyfir_bank_destroy.argtypes = [vp]
+    L.tsdgpu_channelizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
+    L.tsdgpu_channelizer_out_count.argtypes = [vp, i64]
+    L.tsdgpu_channelizer_out_count.restype = i64
+    L.tsdgpu_channelizer_step.argtypes = [vp, vp, i64, vp, i64, i64, C.POINTER(i64), vp]
+    L.tsdgpu_channelizer_reset.argtypes = [vp]
+    L.tsdgpu_channelizer_history_len.argtypes = [vp]
+    L.tsdgpu_channelizer_history_len.restype = i32
+    L.tsdgpu_channelizer_get_state.argtypes = [vp, vp, vp]
+    L.tsdgpu_channelizer_set_state.argtypes = [vp, vp, vp]
+    L.tsdgpu_channelizer_destroy.argtypes = [vp]
     L.tsdgpu_resampler_create.argtypes = [C.POINTER(vp), i32, fl, vp, i32, i32]
     L.tsdgpu_resampler_out_count.argtypes = [vp, i64]
     L.tsdgpu_resampler_out_count.restype = i64
@@ -864,6 +874,66 @@ class PolyFirBank:
     def close(self):
         if self._h:
             lib().tsdgpu_polyfir_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Channelizer:
+    """Maximally decimated polyphase analysis bank (tsdgpu_channelizer): ONE complex64 stream into `channels` = M rows, one
+    launch per step.  step(x) takes n = F M samples and returns the (M, F) block y[c, m] = sum_k h[k] x[n_m - k]
+    exp(-2 pi i c (n_m - k) / M), n_m = m M + M - 1: the (C, n) layout FirBank / SosBank / PolyFirBank read."""
+
+    def __init__(self, taps, channels):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self.channels, self.K = int(channels), len(t)
+        self._h = C.c_void_p()
+        _check(lib().tsdgpu_channelizer_create(C.byref(self._h), self.channels, t.ctypes.data if len(t) else None, len(t)))
+        self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
+
+    def out_count(self, n):
+        return lib().tsdgpu_channelizer_out_count(self._h, int(n))
+
+    def step(self, x, y=None, stream=None):
+        """x: 1-D complex64 numpy array (host) or torch tensor (host or device), a whole number of M-sample frames.
+        y: (M, m) with m >= n / M, of x's kind, rows may be strided (default: a new packed one); returns its (M, n / M) view."""
+        if _dtype_code(x) != C64 or x.ndim != 1:
+            raise TsdGpuError("the channelizer takes a 1-D complex64 stream")
+        n = int(x.shape[0])
+        if y is None:
+            nout = n // self.channels
+            y = np.empty((self.channels, nout), x.dtype) if isinstance(x, np.ndarray) else x.new_empty((self.channels, nout))
+        if _dtype_code(y) != C64:
+            raise TsdGpuError("the channelizer writes complex64 rows")
+        py, ldy = _ptr2d(y, self.channels)
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_channelizer_step(self._h, _ptr(x), n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
+        return y[:, : got.value]
+
+    def reset(self):
+        _check(lib().tsdgpu_channelizer_reset(self._h))
+
+    def get_state(self, dst=None, stream=None):
+        """the last history_len = (P - 1) M input samples, oldest first.  dst: packed numpy array or torch tensor."""
+        if dst is None:
+            dst = np.zeros(self.history_len, np.complex64)
+        assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == C64
+        _check(lib().tsdgpu_channelizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
+        return dst
+
+    def set_state(self, hist=None, stream=None):
+        if self.history_len:
+            assert tuple(hist.shape) == (self.history_len,) and _dtype_code(hist) == C64
+        _check(lib().tsdgpu_channelizer_set_state(self._h, _ptr(hist) if self.history_len else None,
+                                                  _stream_of(hist, stream) if self.history_len else stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_channelizer_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -1,0 +1,356 @@
+// channelizer.hip -- maximally decimated polyphase analysis bank: ONE wideband complex stream into M channel rows.
+//
+//   y_c[m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M),  n_m = m M + M - 1,  c < M
+// computed in the fast form: with P = ceil(K / M), h zero-padded to P M and g_p[s] = h[p M + M - 1 - s],
+//   v_s[m] = sum_{p < P} g_p[s] x[(m - p) M + s],      y_.[m] = DFT_M(v_.[m])  (forward, unscaled).
+// A step of F frames (n = F M samples) writes F outputs to each of the M rows y + c ldy: the (C, n) layout the channel banks read.
+//
+// One persistent kernel.  A workgroup of NT = 512 threads owns R = NT / M streams of frames ("sub-runs": contiguous ranges of
+// 16-frame units; at M = 1024 one sub-run, a thread owning the positions s and s + 512); per iteration every sub-run advances by
+// one unit, so the workgroup's tile is 16 R frames x M channels = 8 Ki points (16 Ki at M = 1024), one LDS image of 68-74 KiB
+// (137 KiB at M = 1024): two workgroups per CU where the registers allow it, one loading while one transforms.
+//  - front: thread (r, s) owns position s of sub-run r.  It loads the unit's samples x[f M + s] in two halves of 8 frames (8
+//    loads in flight; a wave reads 512 contiguous bytes per load from M = 64) and keeps the position's last P - 1 samples in
+//    registers -- the P - 1 halo frames are read from memory only where a sub-run starts: from the handle's history when they lie
+//    before the step -- and forms v_s[f] = fma chain p = P-1 .. 0 (oldest sample first), the same chain for every frame.
+//  - transform: the frame's M points in registers + LDS by s16::transform (M = 16 .. 1024), s16::dft8 (M = 8).
+//  - store: the bins are read back channel-major; a (channel, sub-run) pair receives its 16 frames as one 128-B segment.
+// The last workgroup writes the new history (the last (P - 1) M samples of old history ++ x) into the other buffer.
+#include "common.hpp"
+#include "bank_internal.hpp"
+#include "channelizer_internal.hpp"
+#include "stockham16.hpp"
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+struct tsdgpu_channelizer {
+  int M = 0, lgM = 0, K = 0, P = 0;
+  int HW = 0;                           // history samples: (P - 1) M
+  int FP = 0;                           // pitch of a frame in the LDS image (samples)
+  int cus = 0;
+  float *d_g = nullptr;                 // g[p][s], P rows of M, then the twiddles W_M^i, i < M / 16 (one allocation)
+  tsdgpu::cpx *d_tw = nullptr;
+  void *hist[2] = {nullptr, nullptr};   // HW samples, oldest first (double-buffered, one allocation)
+  int cur = 0;
+  bool attr_set = false;                // the kernel of this shape may take its LDS
+  tsdgpu::DevBuf in_stage, out_stage;
+};
+
+namespace tsdgpu {
+namespace {
+
+constexpr int CHAN_NT = 512;          // threads of a workgroup
+
+// R0 in {16, 8, 4, 2}: M = R0 16^a >= 16 through s16::transform; R0 = 0: M = 8 through s16::dft8.
+// NPOS positions per thread: 1; 2 at M = 1024 (positions s and s + 512, the transforms in two rounds of 8 frames).
+// PP = P, the taps of a polyphase branch: the window and the fma chains are straight-line code in registers.
+template <int R0, int NPOS, int PP>
+__global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restrict__ x, cpx *__restrict__ y, int64_t ldy,
+                                                              const float *__restrict__ gt, const cpx *__restrict__ TW, int M, int lgM,
+                                                              int FP, int64_t F, int64_t per, const cpx *__restrict__ oh,
+                                                              cpx *__restrict__ nh, int al)
+{
+  extern __shared__ __attribute__((aligned(16))) char chan_raw[];
+  cpx *img = reinterpret_cast<cpx *>(chan_raw);
+  constexpr int NT = CHAN_NT;
+  constexpr int PW = PP - 1, PWA = PW > 0 ? PW : 1;      // the window: the last PW samples of the position
+  const int t = threadIdx.x;
+  const int HW = PW * M;
+  const int64_t n = F * M;
+
+  // the new history: the last HW samples of (old history ++ x[0, n))
+  if (blockIdx.x == gridDim.x - 1)
+    for (int i = t; i < HW; i += NT) {
+      const int64_t g = n - HW + i;
+      nh[i] = g < 0 ? oh[HW + g] : x[g];
+    }
+
+  const int s = NPOS == 1 ? t & (M - 1) : t, r = NPOS == 1 ? t >> lgM : 0, R = NPOS == 1 ? NT >> lgM : 1;
+  const int64_t u0 = ((int64_t) blockIdx.x * R + r) * per;           // first unit of the thread's sub-run
+  // frame f of the stream, position s: history before 0; frames from F on (the tail of the last unit, idle sub-runs) read
+  // the last frame and are never stored
+  auto sample = [&](int64_t f, int a) -> cpx {
+    f = min(f, F - 1);
+    const cpx *b = f < 0 ? oh + (f + PW) * M : x + f * M;
+    return b[s + a * NT];
+  };
+  float g[NPOS][PP];
+  cpx prev[NPOS][PWA];
+#pragma unroll
+  for (int a = 0; a < NPOS; a++) {
+#pragma unroll
+    for (int p = 0; p < PP; p++) g[a][p] = gt[p * M + s + a * NT];
+#pragma unroll
+    for (int k = 0; k < PW; k++) prev[a][k] = sample(u0 * 16 - PW + k, a);
+  }
+
+  const int tpt = R0 ? M >> 4 : 1;
+  for (int64_t it = 0; it < per; it++) {
+#pragma unroll
+    for (int a = 0; a < NPOS; a++)
+      for (int h = 0; h < 2; h++) {
+        cpx cur[8];
+        const int64_t f0 = ((u0 + it) << 4) + 8 * h;
+#pragma unroll
+        for (int k = 0; k < 8; k++) cur[k] = sample(f0 + k, a);
+        cpx *dst = img + (r * 16 + 8 * h) * FP + s16::pad(s + a * NT);
+        // v_s[f0 + i] = sum_{p = PP-1 .. 0} g[p] frame(i - p), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest sample first
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          float ar = 0.f, ai = 0.f;
+#pragma unroll
+          for (int p = PP - 1; p >= 0; p--) {
+            const cpx w = i - p >= 0 ? cur[i - p >= 0 ? i - p : 0] : prev[a][i - p < 0 ? PW + i - p : 0];
+            ar = fmaf(g[a][p], w.x, ar);
+            ai = fmaf(g[a][p], w.y, ai);
+          }
+          dst[i * FP] = make_float2(ar, ai);
+        }
+#pragma unroll
+        for (int k = 0; k < PW; k++) prev[a][k] = k + 8 < PW ? prev[a][k + 8 < PW ? k + 8 : 0] : cur[k + 8 >= PW ? k + 8 - PW : 0];
+      }
+    __syncthreads();
+
+    if (R0 == 0) {
+      // M = 8: two frames per thread, each one dft8 (natural order in, natural order out)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        cpx *fr = img + (t + h * NT) * FP;
+        cpx e[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) e[q] = fr[q];
+        s16::dft8(e);
+#pragma unroll
+        for (int q = 0; q < 8; q++) fr[q] = e[q];
+      }
+    } else {
+      const int tl = t >> (lgM - 4), j = t & (tpt - 1);
+#pragma unroll
+      for (int a = 0; a < NPOS; a++) {
+        cpx *fr = img + (tl + a * (NT >> (lgM - 4))) * FP;
+        cpx v[16];
+#pragma unroll
+        for (int m = 0; m < 16; m++) v[m] = fr[s16::pad(j + m * tpt)];
+        __syncthreads();
+        s16::transform<R0 ? R0 : 16>(v, fr, TW, M, j, tpt, [] { __syncthreads(); });
+        // X[j + q tpt] in v[q]: back to the places this thread read last
+#pragma unroll
+        for (int q = 0; q < 16; q++) fr[s16::pad(j + q * tpt)] = v[q];
+      }
+    }
+    __syncthreads();
+
+    // channel-major read-back: item (k, c, rr) = frames 2k, 2k + 1 of sub-run rr's unit, channel c; 8 lanes per 128-B segment
+#pragma unroll 4
+    for (int u = 0; u < 8 * NPOS; u++) {
+      const int e = t + NT * u;
+      const int k = e & 7, c = (e >> 3) & (M - 1), rr = e >> (3 + lgM);
+      const int64_t un = ((int64_t) blockIdx.x * R + rr) * per + it;
+      const int64_t f = (un << 4) + 2 * k;
+      const cpx *src = img + (rr * 16 + 2 * k) * FP + s16::pad(c);
+      const cpx a = src[0], b = src[FP];
+      cpx *yc = y + (int64_t) c * ldy + f;
+      if (f + 1 < F) {
+        if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
+        else { yc[0] = a; yc[1] = b; }
+      } else if (f < F) {
+        yc[0] = a;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int R0, int NPOS, int PP>
+int chan_launch_p(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
+{
+  constexpr int NT = CHAN_NT;
+  const int R = NPOS == 1 ? NT >> c->lgM : 1;
+  const int64_t U = cdiv(F, 16);
+  const int grid = (int) std::min<int64_t>((int64_t) c->cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
+  const int64_t per = cdiv(U, (int64_t) grid * R);
+  const size_t lds = chan_lds_bytes(NT * NPOS, c->M, c->FP);
+  const int al = ((uintptr_t) y & 15) == 0 && (ldy & 1) == 0;
+  if (!c->attr_set) {
+    // (a handle launches one instantiation: asked once, and a refusal is reported here, not as a failed launch)
+    const hipError_t e = hipFuncSetAttribute((const void *) channelizer_kernel<R0, NPOS, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+      (void) hipGetLastError();
+      return set_err(TSDGPU_ERR_HIP, "channelizer_step: the kernel may not take its %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+    }
+    c->attr_set = true;
+  }
+  hipLaunchKernelGGL((channelizer_kernel<R0, NPOS, PP>), dim3(grid), dim3(NT), lds, st, x, y, ldy, c->d_g, c->d_tw, c->M, c->lgM, c->FP, F,
+                     per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], al);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+template <int R0, int NPOS>
+int chan_launch(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
+{
+  switch (c->P) {
+#define CHAN_CASE(PP) case PP: return chan_launch_p<R0, NPOS, PP>(c, x, y, ldy, F, st)
+    CHAN_CASE(1); CHAN_CASE(2); CHAN_CASE(3); CHAN_CASE(4); CHAN_CASE(5); CHAN_CASE(6); CHAN_CASE(7); CHAN_CASE(8);
+    CHAN_CASE(9); CHAN_CASE(10); CHAN_CASE(11); CHAN_CASE(12); CHAN_CASE(13); CHAN_CASE(14); CHAN_CASE(15); CHAN_CASE(16);
+#undef CHAN_CASE
+  }
+  return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P);
+}
+
+size_t hist_bytes(const tsdgpu_channelizer *c) { return (size_t) c->HW * sizeof(cpx); }
+
+}  // namespace
+}  // namespace tsdgpu
+
+using namespace tsdgpu;
+
+extern "C" {
+
+int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps)
+{
+  TSD_CHECK(out != nullptr, "channelizer_create: out is NULL");
+  *out = nullptr;
+  TSD_CHECK(channels >= 1, "channelizer_create: channels = %d, need at least one", channels);
+  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "channelizer_create: K > 0 taps required");
+  if (!chan_served_channels(channels))
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: channels = %d: served are the powers of two from %d to %d", channels,
+                   CHAN_MIN_M, CHAN_MAX_M);
+  if (ntaps > CHAN_MAX_P * channels)
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
+                   ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
+  tsdgpu_channelizer *c = new tsdgpu_channelizer();
+  const int M = channels;
+  c->M = M;
+  c->lgM = __builtin_ctz((unsigned) M);
+  c->K = ntaps;
+  c->P = (ntaps + M - 1) / M;
+  c->HW = (c->P - 1) * M;
+  c->FP = chan_frame_pitch(M);
+  int rc = TSDGPU_OK, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->cus < 1)
+    rc = set_err(TSDGPU_ERR_HIP, "channelizer_create: no device: %s", hipGetErrorString(hipGetLastError()));
+  if (!rc) {
+    // one allocation and one upload: g[p][s] = h[p M + M - 1 - s] (zeros past K), then W_M^i, i < M / 16
+    const size_t ng = (size_t) c->P * M, ntw = (size_t) std::max(M / 16, 1);
+    std::vector<float> image(ng + 2 * ntw, 0.f);
+    for (int p = 0; p < c->P; p++)
+      for (int s = 0; s < M; s++) {
+        const int k = p * M + M - 1 - s;
+        image[(size_t) p * M + s] = k < ntaps ? taps_host[k] : 0.f;
+      }
+    const double PI = 3.14159265358979323846;
+    for (size_t i = 0; i < ntw; i++) {
+      const double a = -2.0 * PI * (double) i / (double) M;
+      image[ng + 2 * i] = (float) std::cos(a);
+      image[ng + 2 * i + 1] = (float) std::sin(a);
+    }
+    const size_t ib = image.size() * sizeof(float), hb = (hist_bytes(c) + 15) / 16 * 16;
+    if (hipMalloc((void **) &c->d_g, ib) != hipSuccess || (hb && hipMalloc(&c->hist[0], 2 * hb) != hipSuccess)) {
+      rc = set_err(TSDGPU_ERR_ALLOC, "channelizer_create: hipMalloc of %zu bytes failed: %s", ib + 2 * hb, hipGetErrorString(hipGetLastError()));
+    } else {
+      c->d_tw = reinterpret_cast<cpx *>(c->d_g + ng);     // (ng is a multiple of 8: 8-B aligned)
+      if (hb) c->hist[1] = (char *) c->hist[0] + hb;
+      if (hipMemcpy(c->d_g, image.data(), ib, hipMemcpyHostToDevice) != hipSuccess || (hb && hipMemset(c->hist[0], 0, 2 * hb) != hipSuccess) ||
+          hipStreamSynchronize(nullptr) != hipSuccess)
+        rc = set_err(TSDGPU_ERR_HIP, "channelizer_create: upload failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+  }
+  if (rc) {
+    tsdgpu_channelizer_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return TSDGPU_OK;
+}
+
+int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n) { return (!c || n < 0) ? -1 : n / c->M; }
+
+int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, void *y, int64_t ldy, int64_t y_capacity, int64_t *n_out,
+                            void *stream)
+{
+  TSD_CHECK(c != nullptr, "channelizer_step: NULL handle");
+  TSD_CHECK(n >= 0, "channelizer_step: negative length");
+  if (n_out) *n_out = 0;
+  if (n == 0) return TSDGPU_OK;
+  TSD_CHECK(n % c->M == 0, "channelizer_step: n = %lld is not a whole number of %d-sample frames", (long long) n, c->M);
+  const int64_t F = n / c->M;
+  TSD_CHECK(x != nullptr && y != nullptr, "channelizer_step: NULL buffer");
+  TSD_CHECK(F <= y_capacity, "channelizer_step: a channel's output needs %lld samples, y_capacity is %lld", (long long) F, (long long) y_capacity);
+  TSD_CHECK(ldy >= F, "channelizer_step: ldy = %lld below the %lld outputs of a channel", (long long) ldy, (long long) F);
+  const size_t sz = sizeof(cpx);
+  TSD_CHECK(!ranges_overlap(x, (size_t) n * sz, y, ((size_t) (c->M - 1) * (size_t) ldy + (size_t) F) * sz),
+            "channelizer_step: x and y overlap (there is no in-place form: the layouts differ)");
+  hipStream_t st = (hipStream_t) stream;
+  const void *dx;
+  void *dy = nullptr;
+  int64_t dldy = F;
+  bool staged = false;
+  int rc;
+  if ((rc = stage_in(x, (size_t) n * sz, c->in_stage, st, &dx))) return rc;
+  if ((rc = bank_stage_out(y, ldy, c->M, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
+  switch (chan_radix0(c->M)) {
+    case 0: rc = chan_launch<0, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
+    case 2: rc = chan_launch<2, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
+    case 4:
+      rc = c->M == 1024 ? chan_launch<4, 2>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st)
+                        : chan_launch<4, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
+      break;
+    case 8: rc = chan_launch<8, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
+    default: rc = chan_launch<16, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
+  }
+  if (rc) return rc;
+  if (c->HW) c->cur ^= 1;
+  if (n_out) *n_out = F;
+  return bank_finish_out(y, ldy, F, c->M, sz, dy, dldy, staged, st);
+}
+
+int tsdgpu_channelizer_reset(tsdgpu_channelizer *c)
+{
+  TSD_CHECK(c != nullptr, "channelizer_reset: NULL handle");
+  if (c->HW) {
+    TSD_HIP(hipMemset(c->hist[c->cur], 0, hist_bytes(c)));
+    TSD_HIP(hipStreamSynchronize(nullptr));      // see tsdgpu_sos_reset
+  }
+  return TSDGPU_OK;
+}
+
+int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c) { return c ? c->HW : -1; }
+
+int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *stream)
+{
+  TSD_CHECK(c != nullptr, "channelizer_get_state: NULL handle");
+  TSD_CHECK(c->HW == 0 || hist_dst != nullptr, "channelizer_get_state: NULL history buffer");
+  if (!c->HW) return TSDGPU_OK;
+  hipStream_t st = (hipStream_t) stream;
+  const bool dev = is_device_ptr(hist_dst);
+  TSD_HIP(hipMemcpyAsync(hist_dst, c->hist[c->cur], hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (!dev) TSD_HIP(hipStreamSynchronize(st));
+  return TSDGPU_OK;
+}
+
+int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, void *stream)
+{
+  TSD_CHECK(c != nullptr, "channelizer_set_state: NULL handle");
+  TSD_CHECK(c->HW == 0 || hist_src != nullptr, "channelizer_set_state: NULL history buffer");
+  if (!c->HW) return TSDGPU_OK;
+  hipStream_t st = (hipStream_t) stream;
+  const bool dev = is_device_ptr(hist_src);
+  TSD_HIP(hipMemcpyAsync(c->hist[c->cur], hist_src, hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  if (!dev) TSD_HIP(hipStreamSynchronize(st));   // (`hist_src` may die with the caller's scope)
+  return TSDGPU_OK;
+}
+
+int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c)
+{
+  if (!c) return TSDGPU_OK;
+  if (c->d_g) (void) hipFree(c->d_g);
+  if (c->hist[0]) (void) hipFree(c->hist[0]);   // (both histories live in the same allocation)
+  c->in_stage.release();
+  c->out_stage.release();
+  delete c;
+  return TSDGPU_OK;
+}
+
+}  // extern "C"

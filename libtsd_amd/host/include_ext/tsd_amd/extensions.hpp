@@ -63,6 +63,15 @@ template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_demi_bande_cana
 template <typename Tc, typename T> sptr<FiltreGen<T>> filtre_rif_ups_canaux(const Vecteur<Tc> &h, entier R, entier nb_canaux);
 template <typename T> sptr<FiltreGen<T>> decimateur_canaux(entier R, entier nb_canaux);
 
+// ---- polyphase channelizer: ONE wideband complex stream into nb_canaux channel rows (include/tsdgpu.h: tsdgpu_channelizer) ----
+// The maximally decimated analysis bank: channel c (centre c / nb_canaux of the input rate) shifted to DC, filtered with the real
+// prototype h, every nb_canaux-th sample kept; no normalisation.  step(x, y): x.rows() a whole number of nb_canaux-sample frames
+// (else échec); y is resized to nb_canaux * (n / nb_canaux), channel after channel: what filtre_rif_canaux::step and the banks
+// above take.  Host or resident vectors; x and y must be different vectors.  The channels of a frame share one transform: the
+// error bound is 1e-5 of the peak over ALL channels, and a NaN / Inf in input frame f reaches every channel of output frames
+// f .. f + ceil(K / nb_canaux) - 1.  Served: nb_canaux a power of two in [8, 1024], K <= 16 nb_canaux; else the factory fails.
+sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux);
+
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
 // every adaptor as input, and as output when it already has the size the step produces (resize() to
