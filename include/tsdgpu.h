@@ -381,6 +381,46 @@ int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, vo
 int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);
 
 /* --------------------------------------------------------------------------------------
+ * Polyphase synthesizer: `channels` = M channel rows into ONE wideband complex64 stream (the
+ * maximally decimated synthesis bank, the dual of the channelizer), one kernel launch per
+ * step.  An extension.  With a real prototype f of K taps, frames counted from creation or
+ * reset and zeros before frame 0, output sample p is
+ *     x[p] = sum_{c<M} exp(+2 pi i c p / M) sum_m u_c[m] f[p - m M]:
+ * row c upsampled by M, filtered with f at baseband, then shifted to c/M of the output rate.
+ * No normalisation: a constant 1 in row c alone gives exp(2 pi i c p / M) sum_j f[j M + p % M].
+ *  - layout: a step of `frames` = F reads F samples from each row u + c*ldu, c < M (ld in
+ *    samples: what a channelizer or a bank of C = M channels wrote, without a copy) and writes
+ *    n = F*M samples of x.  x_capacity is the room of x.  *n_out = F*M.
+ *  - ldu < F, x_capacity < F*M and ANY overlap of the u and x footprints are
+ *    TSDGPU_ERR_INVALID and advance nothing (there is no in-place form: the layouts differ).
+ *    frames == 0 is a no-op.
+ *  - host or device pointers; rows and x need only 8-B alignment (16-B aligned rows -- aligned
+ *    base, even ldu -- take wider loads; the bits are the same).
+ *  - state: the last P - 1 INPUT frames, P = ceil(K / M), as a packed (M, P - 1) block: row c
+ *    holds channel c's last P - 1 samples, oldest first; tsdgpu_synthesizer_history_len() =
+ *    (P - 1) M samples; host or device; 0 samples for K <= M, whose buffer may be NULL.  A
+ *    state moved to a fresh handle continues the stream bit for bit.
+ *  - a stream gives the same bits in one step or in many steps of any frame counts.
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): the channelizer's, M a power
+ *    of two in [8, 1024], K <= 16 M.  M < 1, K < 1 and NULL pointers are TSDGPU_ERR_INVALID.
+ *  - error bound: the samples of a frame share one M-point transform: 1e-5 of the peak of x
+ *    over the step.
+ *  - non-finite inputs: a NaN / Inf anywhere in input frame m makes ALL M samples of output
+ *    frames m .. m + P - 1 non-finite (the shared transform; the zero-padded taps are
+ *    multiplied too) and nothing else: every other output has the bits of the clean run.
+ * ------------------------------------------------------------------------------------ */
+typedef struct tsdgpu_synthesizer tsdgpu_synthesizer;
+int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps);
+int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *s, int64_t frames);  /* frames * channels; advances nothing */
+int tsdgpu_synthesizer_step(tsdgpu_synthesizer *s, const void *u, int64_t ldu, int64_t frames, void *x, int64_t x_capacity,
+                            int64_t *n_out, void *stream);
+int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *s);                                /* history <- zeros */
+int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * channels */
+int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *s, void *hist_dst, void *stream);
+int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *s, const void *hist_src, void *stream);
+int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *s);
+
+/* --------------------------------------------------------------------------------------
  * Resampler:  AdaptationRythmeSimple<T>::step (factory filtre_itrp) over
  *             InterpolateurRIF::step with the LUT-sinc interpolator itrp_sinc
  *             (src/reechan/ra.cc:13-79; include/tsd/filtrage.hpp:1873-1881;

@@ -104,6 +104,16 @@ def _declare(L):
     L.tsdgpu_channelizer_get_state.argtypes = [vp, vp, vp]
     L.tsdgpu_channelizer_set_state.argtypes = [vp, vp, vp]
     L.tsdgpu_channelizer_destroy.argtypes = [vp]
+    L.tsdgpu_synthesizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
+    L.tsdgpu_synthesizer_out_count.argtypes = [vp, i64]
+    L.tsdgpu_synthesizer_out_count.restype = i64
+    L.tsdgpu_synthesizer_step.argtypes = [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp]
+    L.tsdgpu_synthesizer_reset.argtypes = [vp]
+    L.tsdgpu_synthesizer_history_len.argtypes = [vp]
+    L.tsdgpu_synthesizer_history_len.restype = i32
+    L.tsdgpu_synthesizer_get_state.argtypes = [vp, vp, vp]
+    L.tsdgpu_synthesizer_set_state.argtypes = [vp, vp, vp]
+    L.tsdgpu_synthesizer_destroy.argtypes = [vp]
     L.tsdgpu_resampler_create.argtypes = [C.POINTER(vp), i32, fl, vp, i32, i32]
     L.tsdgpu_resampler_out_count.argtypes = [vp, i64]
     L.tsdgpu_resampler_out_count.restype = i64
@@ -934,6 +944,68 @@ class Channelizer:
     def close(self):
         if self._h:
             lib().tsdgpu_channelizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Synthesizer:
+    """Maximally decimated polyphase synthesis bank (tsdgpu_synthesizer), the dual of Channelizer: `channels` = M complex64 rows
+    into ONE stream, one launch per step.  step(u) takes the (M, F) block a Channelizer or a bank wrote and returns the F M
+    samples x[p] = sum_c exp(+2 pi i c p / M) sum_m u[c, m] f[p - m M]."""
+
+    def __init__(self, taps, channels):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self.channels, self.K = int(channels), len(t)
+        self._h = C.c_void_p()
+        _check(lib().tsdgpu_synthesizer_create(C.byref(self._h), self.channels, t.ctypes.data if len(t) else None, len(t)))
+        self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
+        self.frames_kept = self.history_len // self.channels            # P - 1
+
+    def out_count(self, frames):
+        return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
+
+    def step(self, u, x=None, stream=None):
+        """u: (M, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
+        x: 1-D with at least F M samples, of u's kind (default: a new one); returns its first F M samples."""
+        if _dtype_code(u) != C64 or u.ndim != 2:
+            raise TsdGpuError("the synthesizer takes a 2-D (channels, frames) complex64 block")
+        pu, ldu = _ptr2d(u, self.channels)
+        F = int(u.shape[1])
+        if x is None:
+            x = np.empty(F * self.channels, u.dtype) if isinstance(u, np.ndarray) else u.new_empty(F * self.channels)
+        if _dtype_code(x) != C64 or x.ndim != 1:
+            raise TsdGpuError("the synthesizer writes a 1-D complex64 stream")
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_synthesizer_step(self._h, pu, ldu, F, _ptr(x), int(x.shape[0]), C.byref(got), _stream_of(u, stream)))
+        return x[: got.value]
+
+    def reset(self):
+        _check(lib().tsdgpu_synthesizer_reset(self._h))
+
+    def get_state(self, dst=None, stream=None):
+        """the last P - 1 input frames as an (M, P - 1) block: row c = channel c's last inputs, oldest first.
+        dst: packed numpy array or torch tensor."""
+        shape = (self.channels, self.frames_kept)
+        if dst is None:
+            dst = np.zeros(shape, np.complex64)
+        assert tuple(dst.shape) == shape and _dtype_code(dst) == C64
+        _check(lib().tsdgpu_synthesizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
+        return dst
+
+    def set_state(self, hist=None, stream=None):
+        if self.history_len:
+            assert tuple(hist.shape) == (self.channels, self.frames_kept) and _dtype_code(hist) == C64
+        _check(lib().tsdgpu_synthesizer_set_state(self._h, _ptr(hist) if self.history_len else None,
+                                                  _stream_of(hist, stream) if self.history_len else stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_synthesizer_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -72,6 +72,15 @@ template <typename T> sptr<FiltreGen<T>> decimateur_canaux(entier R, entier nb_c
 // f .. f + ceil(K / nb_canaux) - 1.  Served: nb_canaux a power of two in [8, 1024], K <= 16 nb_canaux; else the factory fails.
 sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux);
 
+// ---- polyphase synthesizer: nb_canaux channel rows into ONE wideband complex stream (include/tsdgpu.h: tsdgpu_synthesizer) ----
+// The maximally decimated synthesis bank, the dual of canaliseur_polyphase: channel c upsampled by nb_canaux, filtered at baseband
+// with the real prototype h, shifted to c / nb_canaux of the output rate, the channels summed; no normalisation.  step(x, y):
+// x.rows() = nb_canaux blocks of F samples, channel after channel (else échec): what canaliseur_polyphase::step and the banks
+// above produce; y is resized to nb_canaux * F.  Host or resident vectors; x and y must be different vectors.  The samples of a
+// frame share one transform: the error bound is 1e-5 of the peak of the step, and a NaN / Inf in input frame m reaches every
+// sample of output frames m .. m + ceil(K / nb_canaux) - 1.  Served: nb_canaux a power of two in [8, 1024], K <= 16 nb_canaux.
+sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux);
+
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
 // every adaptor as input, and as output when it already has the size the step produces (resize() to
