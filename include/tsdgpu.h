@@ -368,14 +368,42 @@ int tsdgpu_polyfir_bank_destroy(tsdgpu_polyfir_bank *b);
  *  - non-finite inputs: a NaN / Inf in input frame f makes ALL channels of output frames
  *    f .. f + P - 1 non-finite (the shared transform; the zero-padded taps of the last branch are
  *    multiplied too) and nothing else: every other output has the bits of the clean run.
+ *
+ * Oversampled bank (tsdgpu_channelizer_create_oversampled): the same M channels with a new
+ * frame every D = M / OS samples, OS = `oversample` in {1, 2, 4}; each row keeps a clean band
+ * around its centre, for a per-channel bank to filter and decimate.  The definition above
+ * with n_m = m D + D - 1: every D-th sample kept.  OS = 1 is tsdgpu_channelizer_create, its
+ * kernel and its bits.  What changes for a handle with OS > 1:
+ *  - a step takes n = F*D samples (F whole hops; tsdgpu_channelizer_hop() = D) and writes F
+ *    outputs per row; n % D != 0 is TSDGPU_ERR_INVALID; out_count returns n / D; y_capacity,
+ *    ldy and the overlap check are against F = n / D.
+ *  - state, two parts.  History: the last tsdgpu_channelizer_history_len() = P M - D input
+ *    samples, oldest first (the zero-padded taps of the last branch are multiplied too, so it
+ *    is sized from P, not from K; never empty for OS > 1).  Phase: the hops consumed so far,
+ *    modulo OS (the frame is rotated by ((m + 1) D) mod M before its transform); kept in the
+ *    handle, advanced by F mod OS by a successful step, left alone by a failed one and by
+ *    n == 0, cleared by reset.  To move a stream to a fresh handle, move both: get_state /
+ *    set_state and get_phase / set_phase (any hop count >= 0, taken modulo OS; a negative one
+ *    is TSDGPU_ERR_INVALID).
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [8, 1024], OS in {1, 2, 4}, K <= 16 D.  OS < 1 is TSDGPU_ERR_INVALID.  Rational
+ *    oversampling (4/3, 8/7) is not served.
+ *  - non-finite inputs: a NaN / Inf at stream position q makes ALL channels of output frames
+ *    floor(q / D) .. floor((q + P M) / D) - 1 non-finite (P OS frames) and nothing else.
+ *  - chunk invariance, layouts, alignment and the error bound are those above.
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_channelizer tsdgpu_channelizer;
 int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps);
-int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n);   /* n / channels; advances nothing */
+int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host,
+                                          int ntaps);
+int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c);                        /* D = channels / oversample */
+int tsdgpu_channelizer_get_phase(const tsdgpu_channelizer *c);                  /* hops consumed, modulo OS */
+int tsdgpu_channelizer_set_phase(tsdgpu_channelizer *c, int64_t hops);          /* taken modulo OS */
+int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n);   /* n / hop; advances nothing */
 int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, void *y, int64_t ldy, int64_t y_capacity,
                             int64_t *n_out, void *stream);
-int tsdgpu_channelizer_reset(tsdgpu_channelizer *c);                            /* history <- zeros */
-int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c);                /* (P - 1) * channels */
+int tsdgpu_channelizer_reset(tsdgpu_channelizer *c);                            /* history <- zeros, phase <- 0 */
+int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c);                /* P * channels - hop */
 int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *stream);
 int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, void *stream);
 int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);

@@ -95,6 +95,12 @@ def _declare(L):
     L.tsdgpu_polyfir_bank_set_state.argtypes = [vp, vp, i32, vp]
     L.tsdgpu_polyfir_bank_destroy.argtypes = [vp]
     L.tsdgpu_channelizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
+    L.tsdgpu_channelizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_channelizer_hop.argtypes = [vp]
+    L.tsdgpu_channelizer_hop.restype = i32
+    L.tsdgpu_channelizer_get_phase.argtypes = [vp]
+    L.tsdgpu_channelizer_get_phase.restype = i32
+    L.tsdgpu_channelizer_set_phase.argtypes = [vp, i64]
     L.tsdgpu_channelizer_out_count.argtypes = [vp, i64]
     L.tsdgpu_channelizer_out_count.restype = i64
     L.tsdgpu_channelizer_step.argtypes = [vp, vp, i64, vp, i64, i64, C.POINTER(i64), vp]
@@ -894,28 +900,44 @@ class PolyFirBank:
 
 
 class Channelizer:
-    """Maximally decimated polyphase analysis bank (tsdgpu_channelizer): ONE complex64 stream into `channels` = M rows, one
-    launch per step.  step(x) takes n = F M samples and returns the (M, F) block y[c, m] = sum_k h[k] x[n_m - k]
-    exp(-2 pi i c (n_m - k) / M), n_m = m M + M - 1: the (C, n) layout FirBank / SosBank / PolyFirBank read."""
+    """Polyphase analysis bank (tsdgpu_channelizer): ONE complex64 stream into `channels` = M rows, one launch per step.
+    `oversample` = OS in {1, 2, 4}: a new frame every hop D = M / OS samples (1: the maximally decimated bank).  step(x) takes
+    n = F D samples and returns the (M, F) block y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m D + D - 1:
+    the (C, n) layout FirBank / SosBank / PolyFirBank read.  For OS > 1 the state is the history and `phase`, the hops consumed
+    so far modulo OS: move both to continue a stream in a fresh handle."""
 
-    def __init__(self, taps, channels):
+    def __init__(self, taps, channels, oversample=1):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        self.channels, self.K = int(channels), len(t)
+        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
         self._h = C.c_void_p()
-        _check(lib().tsdgpu_channelizer_create(C.byref(self._h), self.channels, t.ctypes.data if len(t) else None, len(t)))
+        pt = t.ctypes.data if len(t) else None
+        if self.oversample == 1:
+            _check(lib().tsdgpu_channelizer_create(C.byref(self._h), self.channels, pt, len(t)))
+        else:
+            _check(lib().tsdgpu_channelizer_create_oversampled(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
         self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
+        self.hop = lib().tsdgpu_channelizer_hop(self._h)
+
+    @property
+    def phase(self):
+        """hops consumed so far, modulo `oversample`"""
+        return lib().tsdgpu_channelizer_get_phase(self._h)
+
+    @phase.setter
+    def phase(self, hops):
+        _check(lib().tsdgpu_channelizer_set_phase(self._h, int(hops)))
 
     def out_count(self, n):
         return lib().tsdgpu_channelizer_out_count(self._h, int(n))
 
     def step(self, x, y=None, stream=None):
-        """x: 1-D complex64 numpy array (host) or torch tensor (host or device), a whole number of M-sample frames.
-        y: (M, m) with m >= n / M, of x's kind, rows may be strided (default: a new packed one); returns its (M, n / M) view."""
+        """x: 1-D complex64 numpy array (host) or torch tensor (host or device), a whole number of hops of D samples.
+        y: (M, m) with m >= n / D, of x's kind, rows may be strided (default: a new packed one); returns its (M, n / D) view."""
         if _dtype_code(x) != C64 or x.ndim != 1:
             raise TsdGpuError("the channelizer takes a 1-D complex64 stream")
         n = int(x.shape[0])
         if y is None:
-            nout = n // self.channels
+            nout = n // self.hop
             y = np.empty((self.channels, nout), x.dtype) if isinstance(x, np.ndarray) else x.new_empty((self.channels, nout))
         if _dtype_code(y) != C64:
             raise TsdGpuError("the channelizer writes complex64 rows")
@@ -928,7 +950,7 @@ class Channelizer:
         _check(lib().tsdgpu_channelizer_reset(self._h))
 
     def get_state(self, dst=None, stream=None):
-        """the last history_len = (P - 1) M input samples, oldest first.  dst: packed numpy array or torch tensor."""
+        """the last history_len = P M - D input samples, oldest first.  dst: packed numpy array or torch tensor."""
         if dst is None:
             dst = np.zeros(self.history_len, np.complex64)
         assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == C64

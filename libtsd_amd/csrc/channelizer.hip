@@ -16,31 +16,18 @@
 //  - transform: the frame's M points in registers + LDS by s16::transform (M = 16 .. 1024), s16::dft8 (M = 8).
 //  - store: the bins are read back channel-major; a (channel, sub-run) pair receives its 16 frames as one 128-B segment.
 // The last workgroup writes the new history (the last (P - 1) M samples of old history ++ x) into the other buffer.
+// The handle also serves the oversampled bank (hop D = M / OS, OS in {2, 4}): its kernel family is channelizer_os.hip, and the
+// entry points below count a step in hops of D samples; at OS = 1 they are what they were.
 #include "common.hpp"
 #include "bank_internal.hpp"
-#include "channelizer_internal.hpp"
+#include "channelizer_handle.hpp"
 #include "stockham16.hpp"
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-struct tsdgpu_channelizer {
-  int M = 0, lgM = 0, K = 0, P = 0;
-  int HW = 0;                           // history samples: (P - 1) M
-  int FP = 0;                           // pitch of a frame in the LDS image (samples)
-  int cus = 0;
-  float *d_g = nullptr;                 // g[p][s], P rows of M, then the twiddles W_M^i, i < M / 16 (one allocation)
-  tsdgpu::cpx *d_tw = nullptr;
-  void *hist[2] = {nullptr, nullptr};   // HW samples, oldest first (double-buffered, one allocation)
-  int cur = 0;
-  bool attr_set = false;                // the kernel of this shape may take its LDS
-  tsdgpu::DevBuf in_stage, out_stage;
-};
-
 namespace tsdgpu {
 namespace {
-
-constexpr int CHAN_NT = 512;          // threads of a workgroup
 
 // R0 in {16, 8, 4, 2}: M = R0 16^a >= 16 through s16::transform; R0 = 0: M = 8 through s16::dft8.
 // NPOS positions per thread: 1; 2 at M = 1024 (positions s and s + 512, the transforms in two rounds of 8 frames).
@@ -210,23 +197,38 @@ extern "C" {
 
 int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps)
 {
+  return tsdgpu_channelizer_create_oversampled(out, channels, 1, taps_host, ntaps);
+}
+
+int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
   TSD_CHECK(out != nullptr, "channelizer_create: out is NULL");
   *out = nullptr;
   TSD_CHECK(channels >= 1, "channelizer_create: channels = %d, need at least one", channels);
+  TSD_CHECK(oversample >= 1, "channelizer_create: oversample = %d, need at least one", oversample);
   TSD_CHECK(taps_host != nullptr && ntaps >= 1, "channelizer_create: K > 0 taps required");
   if (!chan_served_channels(channels))
     return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: channels = %d: served are the powers of two from %d to %d", channels,
                    CHAN_MIN_M, CHAN_MAX_M);
-  if (ntaps > CHAN_MAX_P * channels)
+  if (!chan_served_oversample(oversample))
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: oversample = %d: served are 1, 2 and 4", oversample);
+  // K <= 16 D: P OS <= 16, the register window of a position stays within 15 older samples
+  if (oversample == 1 && ntaps > CHAN_MAX_P * channels)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
                    ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
+  if (ntaps > CHAN_MAX_P * (channels / oversample))
+    return set_err(TSDGPU_ERR_UNSUPPORTED,
+                   "channelizer_create: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)", ntaps, channels,
+                   channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
   tsdgpu_channelizer *c = new tsdgpu_channelizer();
   const int M = channels;
   c->M = M;
   c->lgM = __builtin_ctz((unsigned) M);
+  c->OS = oversample;
+  c->D = M / oversample;
   c->K = ntaps;
   c->P = (ntaps + M - 1) / M;
-  c->HW = (c->P - 1) * M;
+  c->HW = c->P * M - c->D;
   c->FP = chan_frame_pitch(M);
   int rc = TSDGPU_OK, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->cus < 1)
@@ -265,7 +267,7 @@ int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const floa
   return TSDGPU_OK;
 }
 
-int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n) { return (!c || n < 0) ? -1 : n / c->M; }
+int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n) { return (!c || n < 0) ? -1 : n / c->D; }
 
 int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, void *y, int64_t ldy, int64_t y_capacity, int64_t *n_out,
                             void *stream)
@@ -274,8 +276,9 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   TSD_CHECK(n >= 0, "channelizer_step: negative length");
   if (n_out) *n_out = 0;
   if (n == 0) return TSDGPU_OK;
-  TSD_CHECK(n % c->M == 0, "channelizer_step: n = %lld is not a whole number of %d-sample frames", (long long) n, c->M);
-  const int64_t F = n / c->M;
+  TSD_CHECK(n % c->D == 0, "channelizer_step: n = %lld is not a whole number of %d-sample %s", (long long) n, c->D,
+            c->OS == 1 ? "frames" : "hops");
+  const int64_t F = n / c->D;
   TSD_CHECK(x != nullptr && y != nullptr, "channelizer_step: NULL buffer");
   TSD_CHECK(F <= y_capacity, "channelizer_step: a channel's output needs %lld samples, y_capacity is %lld", (long long) F, (long long) y_capacity);
   TSD_CHECK(ldy >= F, "channelizer_step: ldy = %lld below the %lld outputs of a channel", (long long) ldy, (long long) F);
@@ -290,7 +293,8 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   int rc;
   if ((rc = stage_in(x, (size_t) n * sz, c->in_stage, st, &dx))) return rc;
   if ((rc = bank_stage_out(y, ldy, c->M, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
-  switch (chan_radix0(c->M)) {
+  if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
+  else switch (chan_radix0(c->M)) {
     case 0: rc = chan_launch<0, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
     case 2: rc = chan_launch<2, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
     case 4:
@@ -302,6 +306,7 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   }
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
+  c->phase = (int) ((c->phase + F) % c->OS);
   if (n_out) *n_out = F;
   return bank_finish_out(y, ldy, F, c->M, sz, dy, dldy, staged, st);
 }
@@ -313,10 +318,23 @@ int tsdgpu_channelizer_reset(tsdgpu_channelizer *c)
     TSD_HIP(hipMemset(c->hist[c->cur], 0, hist_bytes(c)));
     TSD_HIP(hipStreamSynchronize(nullptr));      // see tsdgpu_sos_reset
   }
+  c->phase = 0;
   return TSDGPU_OK;
 }
 
 int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c) { return c ? c->HW : -1; }
+
+int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c) { return c ? c->D : -1; }
+
+int tsdgpu_channelizer_get_phase(const tsdgpu_channelizer *c) { return c ? c->phase : -1; }
+
+int tsdgpu_channelizer_set_phase(tsdgpu_channelizer *c, int64_t hops)
+{
+  TSD_CHECK(c != nullptr, "channelizer_set_phase: NULL handle");
+  TSD_CHECK(hops >= 0, "channelizer_set_phase: %lld hops, a negative count", (long long) hops);
+  c->phase = (int) (hops % c->OS);
+  return TSDGPU_OK;
+}
 
 int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *stream)
 {

@@ -5,9 +5,12 @@
 namespace tsdgpu {
 
 constexpr int CHAN_MIN_M = 8, CHAN_MAX_M = 1024;   // channels: a power of two in this range
-constexpr int CHAN_MAX_P = 16;                     // taps per channel (polyphase branches' length): K <= 16 M
+constexpr int CHAN_MAX_P = 16;                     // taps per hop sample: K <= 16 D, D = M / OS the hop (K <= 16 M at OS = 1)
 
 inline bool chan_served_channels(int M) { return M >= CHAN_MIN_M && M <= CHAN_MAX_M && (M & (M - 1)) == 0; }
+
+// oversampling OS = M / D of the analysis bank: 1 (maximally decimated), 2, 4
+inline bool chan_served_oversample(int OS) { return OS == 1 || OS == 2 || OS == 4; }
 
 // first radix of the transform M = R0 16^a (stockham16.hpp); 0: M = 8, one dft8 per frame
 inline int chan_radix0(int M)

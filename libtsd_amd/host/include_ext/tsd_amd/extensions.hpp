@@ -71,6 +71,12 @@ template <typename T> sptr<FiltreGen<T>> decimateur_canaux(entier R, entier nb_c
 // error bound is 1e-5 of the peak over ALL channels, and a NaN / Inf in input frame f reaches every channel of output frames
 // f .. f + ceil(K / nb_canaux) - 1.  Served: nb_canaux a power of two in [8, 1024], K <= 16 nb_canaux; else the factory fails.
 sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux);
+// The same bank oversampled by surech = OS in {1, 2, 4}: a frame every D = nb_canaux / OS samples, so that each row keeps a clean
+// band around its centre for a per-channel bank to filter and decimate.  step(x, y): x.rows() a whole number of hops of D samples
+// (else échec); y is resized to nb_canaux * (n / D), channel after channel.  The object carries the history and the phase of the
+// hop; a NaN / Inf at stream position q reaches every channel of output frames floor(q / D) .. floor((q + P nb_canaux) / D) - 1,
+// P = ceil(K / nb_canaux).  Served: nb_canaux as above, K <= 16 D; else the factory fails.  surech = 1 is the factory above.
+sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux, entier surech);
 
 // ---- polyphase synthesizer: nb_canaux channel rows into ONE wideband complex stream (include/tsdgpu.h: tsdgpu_synthesizer) ----
 // The maximally decimated synthesis bank, the dual of canaliseur_polyphase: channel c upsampled by nb_canaux, filtered at baseband
