@@ -18,13 +18,12 @@
 // The last workgroup writes the new history (the last (P - 1) M samples of old history ++ x) into the other buffer.
 // The handle also serves the oversampled bank (hop D = M / OS, OS in {2, 4}): its kernel family is channelizer_os.hip, and the
 // entry points below count a step in hops of D samples; at OS = 1 they are what they were.
+// Shared with channelizer_os.hip and synthesizer.hip: polybank_tile.hpp (device; it says why the transform block is not in it) and
+// polybank_host.hpp (the handle: what it holds, how it is filled, launched and moved).
 #include "common.hpp"
 #include "bank_internal.hpp"
 #include "channelizer_handle.hpp"
-#include "stockham16.hpp"
-#include <algorithm>
-#include <cmath>
-#include <vector>
+#include "polybank_tile.hpp"
 
 namespace tsdgpu {
 namespace {
@@ -53,8 +52,8 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
       nh[i] = g < 0 ? oh[HW + g] : x[g];
     }
 
-  const int s = NPOS == 1 ? t & (M - 1) : t, r = NPOS == 1 ? t >> lgM : 0, R = NPOS == 1 ? NT >> lgM : 1;
-  const int64_t u0 = ((int64_t) blockIdx.x * R + r) * per;           // first unit of the thread's sub-run
+  const SubRun sr = sub_run<NPOS>(t, M, lgM, per);
+  const int s = sr.s, r = sr.r;
   // frame f of the stream, position s: history before 0; frames from F on (the tail of the last unit, idle sub-runs) read
   // the last frame and are never stored
   auto sample = [&](int64_t f, int a) -> cpx {
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
 #pragma unroll
     for (int p = 0; p < PP; p++) g[a][p] = gt[p * M + s + a * NT];
 #pragma unroll
-    for (int k = 0; k < PW; k++) prev[a][k] = sample(u0 * 16 - PW + k, a);
+    for (int k = 0; k < PW; k++) prev[a][k] = sample(sr.u0 * 16 - PW + k, a);
   }
 
   const int tpt = R0 ? M >> 4 : 1;
@@ -78,24 +77,14 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
     for (int a = 0; a < NPOS; a++)
       for (int h = 0; h < 2; h++) {
         cpx cur[8];
-        const int64_t f0 = ((u0 + it) << 4) + 8 * h;
+        const int64_t f0 = ((sr.u0 + it) << 4) + 8 * h;
 #pragma unroll
         for (int k = 0; k < 8; k++) cur[k] = sample(f0 + k, a);
         cpx *dst = img + (r * 16 + 8 * h) * FP + s16::pad(s + a * NT);
-        // v_s[f0 + i] = sum_{p = PP-1 .. 0} g[p] frame(i - p), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest sample first
+        // v_s[f0 + i] = sum_p g[p] frame(i - p), oldest sample first
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          float ar = 0.f, ai = 0.f;
-#pragma unroll
-          for (int p = PP - 1; p >= 0; p--) {
-            const cpx w = i - p >= 0 ? cur[i - p >= 0 ? i - p : 0] : prev[a][i - p < 0 ? PW + i - p : 0];
-            ar = fmaf(g[a][p], w.x, ar);
-            ai = fmaf(g[a][p], w.y, ai);
-          }
-          dst[i * FP] = make_float2(ar, ai);
-        }
-#pragma unroll
-        for (int k = 0; k < PW; k++) prev[a][k] = k + 8 < PW ? prev[a][k + 8 < PW ? k + 8 : 0] : cur[k + 8 >= PW ? k + 8 - PW : 0];
+        for (int i = 0; i < 8; i++) dst[i * FP] = window_chain<PP, 1>(g[a], prev[a], cur, i);
+        window_shift<PW>(prev[a], cur);
       }
     __syncthreads();
 
@@ -128,23 +117,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
     }
     __syncthreads();
 
-    // channel-major read-back: item (k, c, rr) = frames 2k, 2k + 1 of sub-run rr's unit, channel c; 8 lanes per 128-B segment
-#pragma unroll 4
-    for (int u = 0; u < 8 * NPOS; u++) {
-      const int e = t + NT * u;
-      const int k = e & 7, c = (e >> 3) & (M - 1), rr = e >> (3 + lgM);
-      const int64_t un = ((int64_t) blockIdx.x * R + rr) * per + it;
-      const int64_t f = (un << 4) + 2 * k;
-      const cpx *src = img + (rr * 16 + 2 * k) * FP + s16::pad(c);
-      const cpx a = src[0], b = src[FP];
-      cpx *yc = y + (int64_t) c * ldy + f;
-      if (f + 1 < F) {
-        if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
-        else { yc[0] = a; yc[1] = b; }
-      } else if (f < F) {
-        yc[0] = a;
-      }
-    }
+    store_rows<NPOS>(img, y, ldy, M, lgM, FP, F, per, it, sr.R, al, t);
     __syncthreads();
   }
 }
@@ -152,24 +125,10 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
 template <int R0, int NPOS, int PP>
 int chan_launch_p(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  constexpr int NT = CHAN_NT;
-  const int R = NPOS == 1 ? NT >> c->lgM : 1;
-  const int64_t U = cdiv(F, 16);
-  const int grid = (int) std::min<int64_t>((int64_t) c->cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
-  const int64_t per = cdiv(U, (int64_t) grid * R);
-  const size_t lds = chan_lds_bytes(NT * NPOS, c->M, c->FP);
-  const int al = ((uintptr_t) y & 15) == 0 && (ldy & 1) == 0;
-  if (!c->attr_set) {
-    // (a handle launches one instantiation: asked once, and a refusal is reported here, not as a failed launch)
-    const hipError_t e = hipFuncSetAttribute((const void *) channelizer_kernel<R0, NPOS, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      (void) hipGetLastError();
-      return set_err(TSDGPU_ERR_HIP, "channelizer_step: the kernel may not take its %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-    }
-    c->attr_set = true;
-  }
-  hipLaunchKernelGGL((channelizer_kernel<R0, NPOS, PP>), dim3(grid), dim3(NT), lds, st, x, y, ldy, c->d_g, c->d_tw, c->M, c->lgM, c->FP, F,
-                     per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], al);
+  const PolyLaunch g = polybank_geometry(c, NPOS, F);
+  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_kernel<R0, NPOS, PP>, "channelizer", g.lds)) return rc;
+  hipLaunchKernelGGL((channelizer_kernel<R0, NPOS, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM, c->FP,
+                     F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy));
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
@@ -185,8 +144,6 @@ int chan_launch(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_
   }
   return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P);
 }
-
-size_t hist_bytes(const tsdgpu_channelizer *c) { return (size_t) c->HW * sizeof(cpx); }
 
 }  // namespace
 }  // namespace tsdgpu
@@ -222,43 +179,11 @@ int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels
                    channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
   tsdgpu_channelizer *c = new tsdgpu_channelizer();
   const int M = channels;
-  c->M = M;
-  c->lgM = __builtin_ctz((unsigned) M);
   c->OS = oversample;
   c->D = M / oversample;
-  c->K = ntaps;
-  c->P = (ntaps + M - 1) / M;
-  c->HW = c->P * M - c->D;
-  c->FP = chan_frame_pitch(M);
-  int rc = TSDGPU_OK, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->cus < 1)
-    rc = set_err(TSDGPU_ERR_HIP, "channelizer_create: no device: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc) {
-    // one allocation and one upload: g[p][s] = h[p M + M - 1 - s] (zeros past K), then W_M^i, i < M / 16
-    const size_t ng = (size_t) c->P * M, ntw = (size_t) std::max(M / 16, 1);
-    std::vector<float> image(ng + 2 * ntw, 0.f);
-    for (int p = 0; p < c->P; p++)
-      for (int s = 0; s < M; s++) {
-        const int k = p * M + M - 1 - s;
-        image[(size_t) p * M + s] = k < ntaps ? taps_host[k] : 0.f;
-      }
-    const double PI = 3.14159265358979323846;
-    for (size_t i = 0; i < ntw; i++) {
-      const double a = -2.0 * PI * (double) i / (double) M;
-      image[ng + 2 * i] = (float) std::cos(a);
-      image[ng + 2 * i + 1] = (float) std::sin(a);
-    }
-    const size_t ib = image.size() * sizeof(float), hb = (hist_bytes(c) + 15) / 16 * 16;
-    if (hipMalloc((void **) &c->d_g, ib) != hipSuccess || (hb && hipMalloc(&c->hist[0], 2 * hb) != hipSuccess)) {
-      rc = set_err(TSDGPU_ERR_ALLOC, "channelizer_create: hipMalloc of %zu bytes failed: %s", ib + 2 * hb, hipGetErrorString(hipGetLastError()));
-    } else {
-      c->d_tw = reinterpret_cast<cpx *>(c->d_g + ng);     // (ng is a multiple of 8: 8-B aligned)
-      if (hb) c->hist[1] = (char *) c->hist[0] + hb;
-      if (hipMemcpy(c->d_g, image.data(), ib, hipMemcpyHostToDevice) != hipSuccess || (hb && hipMemset(c->hist[0], 0, 2 * hb) != hipSuccess) ||
-          hipStreamSynchronize(nullptr) != hipSuccess)
-        rc = set_err(TSDGPU_ERR_HIP, "channelizer_create: upload failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
+  // g[p][s] = h[p M + M - 1 - s]; the history is the last P M - D samples of the stream
+  const int rc = polybank_init(c, "channelizer_create", M, taps_host, ntaps, [c, M](int P) { return P * M - c->D; },
+                               [M](int p, int s) { return p * M + M - 1 - s; });
   if (rc) {
     tsdgpu_channelizer_destroy(c);
     return rc;
@@ -294,16 +219,9 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   if ((rc = stage_in(x, (size_t) n * sz, c->in_stage, st, &dx))) return rc;
   if ((rc = bank_stage_out(y, ldy, c->M, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
   if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
-  else switch (chan_radix0(c->M)) {
-    case 0: rc = chan_launch<0, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
-    case 2: rc = chan_launch<2, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
-    case 4:
-      rc = c->M == 1024 ? chan_launch<4, 2>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st)
-                        : chan_launch<4, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
-      break;
-    case 8: rc = chan_launch<8, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
-    default: rc = chan_launch<16, 1>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st); break;
-  }
+  else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
+    return chan_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
+  });
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
   c->phase = (int) ((c->phase + F) % c->OS);
@@ -314,10 +232,7 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
 int tsdgpu_channelizer_reset(tsdgpu_channelizer *c)
 {
   TSD_CHECK(c != nullptr, "channelizer_reset: NULL handle");
-  if (c->HW) {
-    TSD_HIP(hipMemset(c->hist[c->cur], 0, hist_bytes(c)));
-    TSD_HIP(hipStreamSynchronize(nullptr));      // see tsdgpu_sos_reset
-  }
+  if (const int rc = polybank_reset(c)) return rc;
   c->phase = 0;
   return TSDGPU_OK;
 }
@@ -340,33 +255,20 @@ int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *st
 {
   TSD_CHECK(c != nullptr, "channelizer_get_state: NULL handle");
   TSD_CHECK(c->HW == 0 || hist_dst != nullptr, "channelizer_get_state: NULL history buffer");
-  if (!c->HW) return TSDGPU_OK;
-  hipStream_t st = (hipStream_t) stream;
-  const bool dev = is_device_ptr(hist_dst);
-  TSD_HIP(hipMemcpyAsync(hist_dst, c->hist[c->cur], hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (!dev) TSD_HIP(hipStreamSynchronize(st));
-  return TSDGPU_OK;
+  return polybank_copy_state(c, hist_dst, nullptr, (hipStream_t) stream);
 }
 
 int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, void *stream)
 {
   TSD_CHECK(c != nullptr, "channelizer_set_state: NULL handle");
   TSD_CHECK(c->HW == 0 || hist_src != nullptr, "channelizer_set_state: NULL history buffer");
-  if (!c->HW) return TSDGPU_OK;
-  hipStream_t st = (hipStream_t) stream;
-  const bool dev = is_device_ptr(hist_src);
-  TSD_HIP(hipMemcpyAsync(c->hist[c->cur], hist_src, hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  if (!dev) TSD_HIP(hipStreamSynchronize(st));   // (`hist_src` may die with the caller's scope)
-  return TSDGPU_OK;
+  return polybank_copy_state(c, nullptr, hist_src, (hipStream_t) stream);
 }
 
 int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c)
 {
   if (!c) return TSDGPU_OK;
-  if (c->d_g) (void) hipFree(c->d_g);
-  if (c->hist[0]) (void) hipFree(c->hist[0]);   // (both histories live in the same allocation)
-  c->in_stage.release();
-  c->out_stage.release();
+  polybank_release(c);
   delete c;
   return TSDGPU_OK;
 }

@@ -1,4 +1,4 @@
-// channelizer_internal.hpp -- the shapes the polyphase channelizer serves and the geometry of its LDS image (channelizer.hip).
+// channelizer_internal.hpp -- the shapes the polyphase banks serve and the geometry of their LDS image.
 #pragma once
 #include <cstddef>
 
@@ -6,6 +6,7 @@ namespace tsdgpu {
 
 constexpr int CHAN_MIN_M = 8, CHAN_MAX_M = 1024;   // channels: a power of two in this range
 constexpr int CHAN_MAX_P = 16;                     // taps per hop sample: K <= 16 D, D = M / OS the hop (K <= 16 M at OS = 1)
+constexpr int CHAN_NT = 512;                       // threads of a workgroup, analysis and synthesis
 
 inline bool chan_served_channels(int M) { return M >= CHAN_MIN_M && M <= CHAN_MAX_M && (M & (M - 1)) == 0; }
 

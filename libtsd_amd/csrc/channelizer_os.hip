@@ -8,7 +8,8 @@
 //
 // The sibling of channelizer_kernel (channelizer.hip), which stays what it is: the same 512-thread workgroup, 16-frame units,
 // R = 512 / M sub-runs, LDS image and pitch, transform and channel-major read-back -- the output side of a tile does not know
-// the bank is oversampled.  What differs is the front:
+// the bank is oversampled: the same functions in both (polybank_tile.hpp), launched through the same host scaffold
+// (polybank_host.hpp).  Two kernels, not one with OS = 1: that was slower at small P.  What differs is the front:
 //  - addressing: thread (r, s) reads x[(f + 1) D - M + s] for frame f of the step, from the handle's history where that lies
 //    before the step (a frame may straddle the two).  Consecutive frames overlap by M - D: a sample is asked for OS times by the
 //    same workgroup within a few loads.
@@ -22,8 +23,7 @@
 //    asks for the next unit's samples before the transform of the current one (AHEAD below); measured, DESIGN 3.12.
 // The last workgroup writes the new history (the last P M - D samples of old history ++ x) into the other buffer.
 #include "channelizer_handle.hpp"
-#include "stockham16.hpp"
-#include <algorithm>
+#include "polybank_tile.hpp"
 
 namespace tsdgpu {
 namespace {
@@ -56,8 +56,8 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
       nh[i] = g < 0 ? oh[HW + g] : x[g];
     }
 
-  const int s = NPOS == 1 ? t & (M - 1) : t, r = NPOS == 1 ? t >> lgM : 0, R = NPOS == 1 ? NT >> lgM : 1;
-  const int64_t u0 = ((int64_t) blockIdx.x * R + r) * per;           // first unit of the thread's sub-run
+  const SubRun sr = sub_run<NPOS>(t, M, lgM, per);
+  const int s = sr.s, r = sr.r;
   // frame f of the step, position s: sample (f + 1) D - M + s of the step, in the history when negative (never before it: f >=
   // -PW); frames from F on (the tail of the last unit, idle sub-runs) read the last frame and are never stored
   auto sample = [&](int64_t f, int a) -> cpx {
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
 #pragma unroll
     for (int p = 0; p < PP; p++) g[a][p] = gt[p * M + s + a * NT];
 #pragma unroll
-    for (int k = 0; k < PW; k++) prev[a][k] = sample(u0 * 16 - PW + k, a);
+    for (int k = 0; k < PW; k++) prev[a][k] = sample(sr.u0 * 16 - PW + k, a);
 #pragma unroll
     for (int j = 0; j < OS; j++) slot[a][j] = s16::pad((s + a * NT + ((phase + 1 + j) & (OS - 1)) * D) & (M - 1));
   }
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
 #pragma unroll
     for (int h = 0; h < 2; h++)
 #pragma unroll
-      for (int k = 0; k < 8; k++) nxt[h][k] = sample((u0 << 4) + 8 * h + k, 0);
+      for (int k = 0; k < 8; k++) nxt[h][k] = sample((sr.u0 << 4) + 8 * h + k, 0);
   }
 
   const int tpt = R0 ? M >> 4 : 1;
@@ -92,31 +92,20 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
     for (int a = 0; a < NPOS; a++)
       for (int h = 0; h < 2; h++) {
         cpx cur[8];
-        const int64_t f0 = ((u0 + it) << 4) + 8 * h;
+        const int64_t f0 = ((sr.u0 + it) << 4) + 8 * h;
 #pragma unroll
         for (int k = 0; k < 8; k++) cur[k] = AHEAD ? nxt[AHEAD ? h : 0][k] : sample(f0 + k, a);
         cpx *dst = img + (r * 16 + 8 * h) * FP;
-        // v_s[f0 + i] = sum_{p = PP-1 .. 0} g[p] frame(i - p OS), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest sample first
+        // v_s[f0 + i] = sum_p g[p] frame(i - p OS), oldest sample first
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          float ar = 0.f, ai = 0.f;
-#pragma unroll
-          for (int p = PP - 1; p >= 0; p--) {
-            const int k = i - p * OS;
-            const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[a][k < 0 ? PW + k : 0];
-            ar = fmaf(g[a][p], w.x, ar);
-            ai = fmaf(g[a][p], w.y, ai);
-          }
-          dst[i * FP + slot[a][i & (OS - 1)]] = make_float2(ar, ai);
-        }
-#pragma unroll
-        for (int k = 0; k < PW; k++) prev[a][k] = k + 8 < PW ? prev[a][k + 8 < PW ? k + 8 : 0] : cur[k + 8 >= PW ? k + 8 - PW : 0];
+        for (int i = 0; i < 8; i++) dst[i * FP + slot[a][i & (OS - 1)]] = window_chain<PP, OS>(g[a], prev[a], cur, i);
+        window_shift<PW>(prev[a], cur);
       }
     if (AHEAD && it + 1 < per) {                                      // (nothing is read for a unit the sub-run does not have)
 #pragma unroll
       for (int h = 0; h < 2; h++)
 #pragma unroll
-        for (int k = 0; k < 8; k++) nxt[h][k] = sample(((u0 + it + 1) << 4) + 8 * h + k, 0);
+        for (int k = 0; k < 8; k++) nxt[h][k] = sample(((sr.u0 + it + 1) << 4) + 8 * h + k, 0);
     }
     __syncthreads();
 
@@ -150,23 +139,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
     }
     __syncthreads();
 
-    // channel-major read-back: item (k, c, rr) = frames 2k, 2k + 1 of sub-run rr's unit, channel c; 8 lanes per 128-B segment
-#pragma unroll 4
-    for (int u = 0; u < 8 * NPOS; u++) {
-      const int e = t + NT * u;
-      const int k = e & 7, c = (e >> 3) & (M - 1), rr = e >> (3 + lgM);
-      const int64_t un = ((int64_t) blockIdx.x * R + rr) * per + it;
-      const int64_t f = (un << 4) + 2 * k;
-      const cpx *src = img + (rr * 16 + 2 * k) * FP + s16::pad(c);
-      const cpx a = src[0], b = src[FP];
-      cpx *yc = y + (int64_t) c * ldy + f;
-      if (f + 1 < F) {
-        if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
-        else { yc[0] = a; yc[1] = b; }
-      } else if (f < F) {
-        yc[0] = a;
-      }
-    }
+    store_rows<NPOS>(img, y, ldy, M, lgM, FP, F, per, it, sr.R, al, t);
     __syncthreads();
   }
 }
@@ -174,24 +147,10 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
 template <int R0, int NPOS, int PP, int OS>
 int chan_os_launch_p(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  constexpr int NT = CHAN_NT;
-  const int R = NPOS == 1 ? NT >> c->lgM : 1;
-  const int64_t U = cdiv(F, 16);
-  const int grid = (int) std::min<int64_t>((int64_t) c->cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
-  const int64_t per = cdiv(U, (int64_t) grid * R);
-  const size_t lds = chan_lds_bytes(NT * NPOS, c->M, c->FP);
-  const int al = ((uintptr_t) y & 15) == 0 && (ldy & 1) == 0;
-  if (!c->attr_set) {
-    // (a handle launches one instantiation: asked once, and a refusal is reported here, not as a failed launch)
-    const hipError_t e = hipFuncSetAttribute((const void *) channelizer_os_kernel<R0, NPOS, PP, OS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      (void) hipGetLastError();
-      return set_err(TSDGPU_ERR_HIP, "channelizer_step: the kernel may not take its %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-    }
-    c->attr_set = true;
-  }
-  hipLaunchKernelGGL((channelizer_os_kernel<R0, NPOS, PP, OS>), dim3(grid), dim3(NT), lds, st, x, y, ldy, c->d_g, c->d_tw, c->M, c->lgM, c->FP,
-                     F, per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], al, c->phase);
+  const PolyLaunch g = polybank_geometry(c, NPOS, F);
+  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_os_kernel<R0, NPOS, PP, OS>, "channelizer", g.lds)) return rc;
+  hipLaunchKernelGGL((channelizer_os_kernel<R0, NPOS, PP, OS>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM,
+                     c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy), c->phase);
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
@@ -212,13 +171,7 @@ int chan_os_launch_r(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, i
 
 int chan_os_launch(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  switch (chan_radix0(c->M)) {
-    case 0: return chan_os_launch_r<0, 1>(c, x, y, ldy, F, st);
-    case 2: return chan_os_launch_r<2, 1>(c, x, y, ldy, F, st);
-    case 4: return c->M == 1024 ? chan_os_launch_r<4, 2>(c, x, y, ldy, F, st) : chan_os_launch_r<4, 1>(c, x, y, ldy, F, st);
-    case 8: return chan_os_launch_r<8, 1>(c, x, y, ldy, F, st);
-    default: return chan_os_launch_r<16, 1>(c, x, y, ldy, F, st);
-  }
+  return polybank_radix(c->M, [&](auto r0, auto npos) { return chan_os_launch_r<decltype(r0)::value, decltype(npos)::value>(c, x, y, ldy, F, st); });
 }
 
 }  // namespace tsdgpu

@@ -1,0 +1,84 @@
+// polybank_tile.hpp -- the device side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip): a
+// workgroup of CHAN_NT threads, R = CHAN_NT / M sub-runs of 16-frame units, one LDS image of 16 R frames at pitch FP
+// (channelizer_internal.hpp).  Here are the thread's place in that tile, the channel-major read-back of the two analysis banks,
+// and the register window of a position with its fma chains.  Where a bank's samples come from and where its frames go stays in
+// its own file, and so does the in-LDS transform of the tile (the R0 == 0 / s16::transform block): the files are built with
+// -ffp-contract=fast, and behind a function the twiddle products of that block fuse differently and give other bits.
+#pragma once
+#include "channelizer_internal.hpp"
+#include "stockham16.hpp"
+
+namespace tsdgpu {
+
+// Thread t: position s of sub-run r of R (NPOS = 2, M = 1024: one sub-run, the positions s and s + CHAN_NT); u0 the first unit of
+// the sub-run, `per` units to a sub-run.
+struct SubRun {
+  int s, r, R;
+  int64_t u0;
+};
+template <int NPOS> __device__ __forceinline__ SubRun sub_run(int t, int M, int lgM, int64_t per)
+{
+  const int s = NPOS == 1 ? t & (M - 1) : t, r = NPOS == 1 ? t >> lgM : 0, R = NPOS == 1 ? CHAN_NT >> lgM : 1;
+  return {s, r, R, ((int64_t) blockIdx.x * R + r) * per};
+}
+
+// Item e of a channel-major pass over the tile of iteration `it`: (k, c, rr) = frames 2k, 2k + 1 of sub-run rr's unit, channel c;
+// f the first of the two, counted in the step (negative in the synthesizer's unit it = -1).  8 lanes per 128-B segment.
+struct TileItem {
+  int k, c, rr;
+  int64_t f;
+};
+__device__ __forceinline__ TileItem tile_item(int e, int M, int lgM, int R, int64_t per, int64_t it)
+{
+  const int k = e & 7, c = (e >> 3) & (M - 1), rr = e >> (3 + lgM);
+  const int64_t un = ((int64_t) blockIdx.x * R + rr) * per + it;
+  return {k, c, rr, (un << 4) + 2 * k};
+}
+
+// channel-major read-back of the transformed tile into the rows y + c ldy: a (channel, sub-run) pair receives its 16 frames as
+// one 128-B segment, 16 B a lane where the rows are 16-B aligned (al), 2 x 8 B where not; frames from F on are not stored
+template <int NPOS>
+__device__ __forceinline__ void store_rows(const cpx *img, cpx *__restrict__ y, int64_t ldy, int M, int lgM, int FP, int64_t F,
+                                           int64_t per, int64_t it, int R, int al, int t)
+{
+#pragma unroll 4
+  for (int u = 0; u < 8 * NPOS; u++) {
+    const TileItem q = tile_item(t + CHAN_NT * u, M, lgM, R, per, it);
+    const cpx *src = img + (q.rr * 16 + 2 * q.k) * FP + s16::pad(q.c);
+    const cpx a = src[0], b = src[FP];
+    cpx *yc = y + (int64_t) q.c * ldy + q.f;
+    if (q.f + 1 < F) {
+      if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
+      else { yc[0] = a; yc[1] = b; }
+    } else if (q.f < F) {
+      yc[0] = a;
+    }
+  }
+}
+
+// The register window of a position: cur[8] its values in the 8 frames of a half unit, prev[PW] those of the PW = (PP - 1) OS
+// frames before, oldest first (OS = 1 where frames do not overlap).  Frame i of the half:
+//   sum_{p = PP-1 .. 0} g[p] frame(i - p OS), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest sample first
+template <int PP, int OS>
+__device__ __forceinline__ cpx window_chain(const float (&g)[PP], const cpx (&prev)[PP > 1 ? (PP - 1) * OS : 1], const cpx (&cur)[8], int i)
+{
+  constexpr int PW = (PP - 1) * OS;
+  float ar = 0.f, ai = 0.f;
+#pragma unroll
+  for (int p = PP - 1; p >= 0; p--) {
+    const int k = i - p * OS;
+    const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[k < 0 ? PW + k : 0];
+    ar = fmaf(g[p], w.x, ar);
+    ai = fmaf(g[p], w.y, ai);
+  }
+  return make_float2(ar, ai);
+}
+
+// the window moves on by the half unit: prev = the last PW of (prev ++ cur)
+template <int PW> __device__ __forceinline__ void window_shift(cpx (&prev)[PW > 0 ? PW : 1], const cpx (&cur)[8])
+{
+#pragma unroll
+  for (int k = 0; k < PW; k++) prev[k] = k + 8 < PW ? prev[k + 8 < PW ? k + 8 : 0] : cur[k + 8 >= PW ? k + 8 - PW : 0];
+}
+
+}  // namespace tsdgpu

@@ -7,7 +7,8 @@
 // A step of F frames reads F samples from each of the M rows u + c ldu and writes n = F M samples of x.
 //
 // One persistent kernel, channelizer_kernel end for end: a workgroup of NT = 512 threads owns R = NT / M sub-runs of 16-frame
-// units (at M = 1024 one sub-run, a thread owning the positions s and s + 512); the LDS image is the channelizer's.
+// units (at M = 1024 one sub-run, a thread owning the positions s and s + 512); the LDS image is the channelizer's.  Shared with
+// the analysis kernels: polybank_tile.hpp (device) and polybank_host.hpp (the handle's host side).
 //  - load: channel-major; a (channel, sub-run) pair gives its 16 frames as one 128-B segment, 8 lanes x 16 B (2 x 8 B where the
 //    rows are not 16-B aligned), written frame-major into the image with re and im swapped.
 //  - transform: the frame's M points by s16::transform (M = 16 .. 1024), s16::dft8 (M = 8): forward on swapped values, which is
@@ -20,40 +21,25 @@
 // old history ++ u, per channel) into the other buffer.
 #include "common.hpp"
 #include "bank_internal.hpp"
-#include "channelizer_internal.hpp"
-#include "stockham16.hpp"
-#include <algorithm>
-#include <cmath>
-#include <vector>
+#include "polybank_host.hpp"
+#include "polybank_tile.hpp"
 
-struct tsdgpu_synthesizer {
-  int M = 0, lgM = 0, K = 0, P = 0;
-  int HW = 0;                           // history samples: (P - 1) M, as an (M, P - 1) block
-  int FP = 0;                           // pitch of a frame in the LDS image (samples)
-  int cus = 0;
-  float *d_f = nullptr;                 // f[j][s], P rows of M, then the twiddles W_M^i, i < M / 16 (one allocation)
-  tsdgpu::cpx *d_tw = nullptr;
-  void *hist[2] = {nullptr, nullptr};   // row c: channel c's last P - 1 inputs, oldest first (double-buffered, one allocation)
-  int cur = 0;
-  bool attr_set = false;                // the kernel of this shape may take its LDS
-  tsdgpu::DevBuf in_stage, out_stage;
-};
+// d_tab: f[j][s] = f[j M + s]; HW = (P - 1) M history samples as an (M, P - 1) block: row c channel c's last P - 1 inputs, oldest first
+struct tsdgpu_synthesizer : tsdgpu::PolyBank {};
 
 namespace tsdgpu {
 namespace {
 
-constexpr int SYN_NT = 512;           // threads of a workgroup
-
 // R0, NPOS, PP: as channelizer_kernel's.
 template <int R0, int NPOS, int PP>
-__global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restrict__ u, int64_t ldu, cpx *__restrict__ x,
+__global__ __launch_bounds__(CHAN_NT) void synthesizer_kernel(const cpx *__restrict__ u, int64_t ldu, cpx *__restrict__ x,
                                                              const float *__restrict__ ft, const cpx *__restrict__ TW, int M, int lgM,
                                                              int FP, int64_t F, int64_t per, const cpx *__restrict__ oh,
                                                              cpx *__restrict__ nh, int al)
 {
   extern __shared__ __attribute__((aligned(16))) char syn_raw[];
   cpx *img = reinterpret_cast<cpx *>(syn_raw);
-  constexpr int NT = SYN_NT;
+  constexpr int NT = CHAN_NT;
   constexpr int PW = PP - 1, PWA = PW > 0 ? PW : 1;      // the window: the last PW transformed frames of the position
   const int t = threadIdx.x;
 
@@ -70,8 +56,8 @@ __global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restri
       nh[i] = fetch(c, F - PW + k);
     }
 
-  const int s = NPOS == 1 ? t & (M - 1) : t, r = NPOS == 1 ? t >> lgM : 0, R = NPOS == 1 ? NT >> lgM : 1;
-  const int64_t u0 = ((int64_t) blockIdx.x * R + r) * per;           // first unit of the thread's sub-run
+  const SubRun sr = sub_run<NPOS>(t, M, lgM, per);
+  const int s = sr.s, r = sr.r;
   float g[NPOS][PP];
   cpx prev[NPOS][PWA];
 #pragma unroll
@@ -88,10 +74,9 @@ __global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restri
     // channel-major load: item (k, c, rr) = frames 2k, 2k + 1 of sub-run rr's unit, channel c; 8 lanes per 128-B segment
 #pragma unroll 4
     for (int v = 0; v < 8 * NPOS; v++) {
-      const int e = t + NT * v;
-      const int k = e & 7, c = (e >> 3) & (M - 1), rr = e >> (3 + lgM);
-      const int64_t un = ((int64_t) blockIdx.x * R + rr) * per + it;
-      const int64_t f = un * 16 + 2 * k;
+      const TileItem q = tile_item(t + NT * v, M, lgM, sr.R, per, it);
+      const int k = q.k, c = q.c, rr = q.rr;
+      const int64_t f = q.f;
       cpx a, b;
       if (al && f >= 0 && f + 1 < F) {
         const float4 q = *reinterpret_cast<const float4 *>(u + (int64_t) c * ldu + f);
@@ -141,7 +126,7 @@ __global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restri
     for (int a = 0; a < NPOS; a++)
       for (int h = 0; h < 2; h++) {
         cpx cur[8];
-        const int64_t f0 = ((u0 + it) * 16) + 8 * h;
+        const int64_t f0 = ((sr.u0 + it) * 16) + 8 * h;
         const cpx *src = img + (r * 16 + 8 * h) * FP + s16::pad(s + a * NT);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -150,21 +135,14 @@ __global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restri
         }
         if (it >= 0) {
           cpx *dst = x + f0 * M + s + a * NT;
-          // x[(f0 + i) M + s] = sum_{j = PP-1 .. 0} g[j] frame(i - j), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest first
+          // x[(f0 + i) M + s] = sum_j g[j] frame(i - j), oldest frame first
 #pragma unroll
           for (int i = 0; i < 8; i++) {
-            float ar = 0.f, ai = 0.f;
-#pragma unroll
-            for (int p = PP - 1; p >= 0; p--) {
-              const cpx w = i - p >= 0 ? cur[i - p >= 0 ? i - p : 0] : prev[a][i - p < 0 ? PW + i - p : 0];
-              ar = fmaf(g[a][p], w.x, ar);
-              ai = fmaf(g[a][p], w.y, ai);
-            }
-            if (f0 + i < F) dst[(int64_t) i * M] = make_float2(ar, ai);
+            const cpx v = window_chain<PP, 1>(g[a], prev[a], cur, i);
+            if (f0 + i < F) dst[(int64_t) i * M] = v;
           }
         }
-#pragma unroll
-        for (int k = 0; k < PW; k++) prev[a][k] = k + 8 < PW ? prev[a][k + 8 < PW ? k + 8 : 0] : cur[k + 8 >= PW ? k + 8 - PW : 0];
+        window_shift<PW>(prev[a], cur);
       }
     __syncthreads();
   }
@@ -173,24 +151,10 @@ __global__ __launch_bounds__(SYN_NT) void synthesizer_kernel(const cpx *__restri
 template <int R0, int NPOS, int PP>
 int syn_launch_p(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
 {
-  constexpr int NT = SYN_NT;
-  const int R = NPOS == 1 ? NT >> c->lgM : 1;
-  const int64_t U = cdiv(F, 16);
-  const int grid = (int) std::min<int64_t>((int64_t) c->cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
-  const int64_t per = cdiv(U, (int64_t) grid * R);
-  const size_t lds = chan_lds_bytes(NT * NPOS, c->M, c->FP);
-  const int al = ((uintptr_t) u & 15) == 0 && (ldu & 1) == 0;
-  if (!c->attr_set) {
-    // (a handle launches one instantiation: asked once, and a refusal is reported here, not as a failed launch)
-    const hipError_t e = hipFuncSetAttribute((const void *) synthesizer_kernel<R0, NPOS, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      (void) hipGetLastError();
-      return set_err(TSDGPU_ERR_HIP, "synthesizer_step: the kernel may not take its %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-    }
-    c->attr_set = true;
-  }
-  hipLaunchKernelGGL((synthesizer_kernel<R0, NPOS, PP>), dim3(grid), dim3(NT), lds, st, u, ldu, x, c->d_f, c->d_tw, c->M, c->lgM, c->FP, F,
-                     per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], al);
+  const PolyLaunch g = polybank_geometry(c, NPOS, F);
+  if (const int rc = polybank_lds_attr(c, (const void *) synthesizer_kernel<R0, NPOS, PP>, "synthesizer", g.lds)) return rc;
+  hipLaunchKernelGGL((synthesizer_kernel<R0, NPOS, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, u, ldu, x, c->d_tab, c->d_tw, c->M, c->lgM, c->FP,
+                     F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu));
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
@@ -206,8 +170,6 @@ int syn_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t
   }
   return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per channel", c->P);
 }
-
-size_t hist_bytes(const tsdgpu_synthesizer *c) { return (size_t) c->HW * sizeof(cpx); }
 
 }  // namespace
 }  // namespace tsdgpu
@@ -230,37 +192,9 @@ int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const floa
                    ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
   tsdgpu_synthesizer *c = new tsdgpu_synthesizer();
   const int M = channels;
-  c->M = M;
-  c->lgM = __builtin_ctz((unsigned) M);
-  c->K = ntaps;
-  c->P = (ntaps + M - 1) / M;
-  c->HW = (c->P - 1) * M;
-  c->FP = chan_frame_pitch(M);
-  int rc = TSDGPU_OK, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->cus < 1)
-    rc = set_err(TSDGPU_ERR_HIP, "synthesizer_create: no device: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc) {
-    // one allocation and one upload: f[j][s] = f[j M + s] (zeros past K), then W_M^i, i < M / 16
-    const size_t ng = (size_t) c->P * M, ntw = (size_t) std::max(M / 16, 1);
-    std::vector<float> image(ng + 2 * ntw, 0.f);
-    std::copy(taps_host, taps_host + ntaps, image.begin());
-    const double PI = 3.14159265358979323846;
-    for (size_t i = 0; i < ntw; i++) {
-      const double a = -2.0 * PI * (double) i / (double) M;
-      image[ng + 2 * i] = (float) std::cos(a);
-      image[ng + 2 * i + 1] = (float) std::sin(a);
-    }
-    const size_t ib = image.size() * sizeof(float), hb = (hist_bytes(c) + 15) / 16 * 16;
-    if (hipMalloc((void **) &c->d_f, ib) != hipSuccess || (hb && hipMalloc(&c->hist[0], 2 * hb) != hipSuccess)) {
-      rc = set_err(TSDGPU_ERR_ALLOC, "synthesizer_create: hipMalloc of %zu bytes failed: %s", ib + 2 * hb, hipGetErrorString(hipGetLastError()));
-    } else {
-      c->d_tw = reinterpret_cast<cpx *>(c->d_f + ng);     // (ng is a multiple of 8: 8-B aligned)
-      if (hb) c->hist[1] = (char *) c->hist[0] + hb;
-      if (hipMemcpy(c->d_f, image.data(), ib, hipMemcpyHostToDevice) != hipSuccess || (hb && hipMemset(c->hist[0], 0, 2 * hb) != hipSuccess) ||
-          hipStreamSynchronize(nullptr) != hipSuccess)
-        rc = set_err(TSDGPU_ERR_HIP, "synthesizer_create: upload failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
+  // f[j][s] = f[j M + s]; the history is the last P - 1 input frames
+  const int rc = polybank_init(c, "synthesizer_create", M, taps_host, ntaps, [M](int P) { return (P - 1) * M; },
+                               [M](int p, int s) { return p * M + s; });
   if (rc) {
     tsdgpu_synthesizer_destroy(c);
     return rc;
@@ -293,16 +227,9 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   int rc;
   if ((rc = bank_stage_in(u, ldu, F, c->M, sz, false, F, c->in_stage, st, &du, &dldu))) return rc;
   if ((rc = stage_out(x, (size_t) n * sz, c->out_stage, &dx, &staged))) return rc;
-  switch (chan_radix0(c->M)) {
-    case 0: rc = syn_launch<0, 1>(c, (const cpx *) du, dldu, (cpx *) dx, F, st); break;
-    case 2: rc = syn_launch<2, 1>(c, (const cpx *) du, dldu, (cpx *) dx, F, st); break;
-    case 4:
-      rc = c->M == 1024 ? syn_launch<4, 2>(c, (const cpx *) du, dldu, (cpx *) dx, F, st)
-                        : syn_launch<4, 1>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
-      break;
-    case 8: rc = syn_launch<8, 1>(c, (const cpx *) du, dldu, (cpx *) dx, F, st); break;
-    default: rc = syn_launch<16, 1>(c, (const cpx *) du, dldu, (cpx *) dx, F, st); break;
-  }
+  rc = polybank_radix(c->M, [&](auto r0, auto npos) {
+    return syn_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
+  });
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
   if (n_out) *n_out = n;
@@ -312,11 +239,7 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
 int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *c)
 {
   TSD_CHECK(c != nullptr, "synthesizer_reset: NULL handle");
-  if (c->HW) {
-    TSD_HIP(hipMemset(c->hist[c->cur], 0, hist_bytes(c)));
-    TSD_HIP(hipStreamSynchronize(nullptr));      // see tsdgpu_sos_reset
-  }
-  return TSDGPU_OK;
+  return polybank_reset(c);
 }
 
 int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *c) { return c ? c->HW : -1; }
@@ -325,33 +248,20 @@ int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *c, void *hist_dst, void *st
 {
   TSD_CHECK(c != nullptr, "synthesizer_get_state: NULL handle");
   TSD_CHECK(c->HW == 0 || hist_dst != nullptr, "synthesizer_get_state: NULL history buffer");
-  if (!c->HW) return TSDGPU_OK;
-  hipStream_t st = (hipStream_t) stream;
-  const bool dev = is_device_ptr(hist_dst);
-  TSD_HIP(hipMemcpyAsync(hist_dst, c->hist[c->cur], hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (!dev) TSD_HIP(hipStreamSynchronize(st));
-  return TSDGPU_OK;
+  return polybank_copy_state(c, hist_dst, nullptr, (hipStream_t) stream);
 }
 
 int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *c, const void *hist_src, void *stream)
 {
   TSD_CHECK(c != nullptr, "synthesizer_set_state: NULL handle");
   TSD_CHECK(c->HW == 0 || hist_src != nullptr, "synthesizer_set_state: NULL history buffer");
-  if (!c->HW) return TSDGPU_OK;
-  hipStream_t st = (hipStream_t) stream;
-  const bool dev = is_device_ptr(hist_src);
-  TSD_HIP(hipMemcpyAsync(c->hist[c->cur], hist_src, hist_bytes(c), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-  if (!dev) TSD_HIP(hipStreamSynchronize(st));   // (`hist_src` may die with the caller's scope)
-  return TSDGPU_OK;
+  return polybank_copy_state(c, nullptr, hist_src, (hipStream_t) stream);
 }
 
 int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *c)
 {
   if (!c) return TSDGPU_OK;
-  if (c->d_f) (void) hipFree(c->d_f);
-  if (c->hist[0]) (void) hipFree(c->hist[0]);   // (both histories live in the same allocation)
-  c->in_stage.release();
-  c->out_stage.release();
+  polybank_release(c);
   delete c;
   return TSDGPU_OK;
 }
