@@ -436,14 +436,44 @@ int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);
  *  - non-finite inputs: a NaN / Inf anywhere in input frame m makes ALL M samples of output
  *    frames m .. m + P - 1 non-finite (the shared transform; the zero-padded taps are
  *    multiplied too) and nothing else: every other output has the bits of the clean run.
+ *
+ * Oversampled bank (tsdgpu_synthesizer_create_oversampled): the rows of an oversampled
+ * channelizer (or of the banks behind it), one frame per hop of D = M / OS output samples,
+ * OS = `oversample` in {1, 2, 4}, back into one stream.  With positions p counted over the
+ * whole stream,
+ *     x[p] = sum_{c<M} exp(+2 pi i c p / M) sum_m u_c[m] f[p - m D]:
+ * row c upsampled by D, not by M.  OS = 1 is tsdgpu_synthesizer_create, its kernel and its
+ * bits.  What changes for a handle with OS > 1:
+ *  - a step of F frames writes n = F*D samples (tsdgpu_synthesizer_hop() = D); out_count
+ *    returns frames * D; x_capacity and the overlap check are against F*D.
+ *  - state, two parts.  History: the last Q - 1 input frames, Q = ceil(K / D), as the packed
+ *    (M, Q - 1) block above; tsdgpu_synthesizer_history_len() = (Q - 1) M.  Phase: the hops
+ *    consumed so far, modulo OS (output q D + s' takes position ((phase + q) D + s') mod M of
+ *    the transformed frames); kept in the handle, advanced by F mod OS by a successful step,
+ *    left alone by a failed one and by frames == 0, cleared by reset.  To move a stream to a
+ *    fresh handle, move both: get_state / set_state and get_phase / set_phase (any hop count
+ *    >= 0, taken modulo OS; a negative one is TSDGPU_ERR_INVALID).
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [8, 1024], OS in {1, 2, 4}, K <= 16 D.  OS < 1 is TSDGPU_ERR_INVALID.  Rational
+ *    oversampling is not served.
+ *  - non-finite inputs: a NaN / Inf anywhere in input frame m makes ALL D samples of output
+ *    hops m .. m + Q - 1 non-finite and nothing else.
+ *  - reconstruction: with h[k] = sin(pi (k + 1/2) / M), k < M, in the channelizer, f = h
+ *    reversed here and the rows delayed by one frame, x comes back as (M OS / 2) x[p - M].
+ *  - chunk invariance, layouts, alignment and the error bound are those above.
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_synthesizer tsdgpu_synthesizer;
 int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps);
-int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *s, int64_t frames);  /* frames * channels; advances nothing */
+int tsdgpu_synthesizer_create_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host,
+                                          int ntaps);
+int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *s);                            /* D = channels / oversample */
+int tsdgpu_synthesizer_get_phase(const tsdgpu_synthesizer *s);                      /* hops consumed, modulo OS */
+int tsdgpu_synthesizer_set_phase(tsdgpu_synthesizer *s, int64_t hops);              /* taken modulo OS */
+int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *s, int64_t frames);  /* frames * hop; advances nothing */
 int tsdgpu_synthesizer_step(tsdgpu_synthesizer *s, const void *u, int64_t ldu, int64_t frames, void *x, int64_t x_capacity,
                             int64_t *n_out, void *stream);
-int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *s);                                /* history <- zeros */
-int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * channels */
+int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *s);                                /* history <- zeros, phase <- 0 */
+int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * channels; OS > 1: (Q - 1) * channels */
 int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *s, void *hist_dst, void *stream);
 int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *s, const void *hist_src, void *stream);
 int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *s);

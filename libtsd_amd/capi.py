@@ -111,6 +111,12 @@ def _declare(L):
     L.tsdgpu_channelizer_set_state.argtypes = [vp, vp, vp]
     L.tsdgpu_channelizer_destroy.argtypes = [vp]
     L.tsdgpu_synthesizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
+    L.tsdgpu_synthesizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_synthesizer_hop.argtypes = [vp]
+    L.tsdgpu_synthesizer_hop.restype = i32
+    L.tsdgpu_synthesizer_get_phase.argtypes = [vp]
+    L.tsdgpu_synthesizer_get_phase.restype = i32
+    L.tsdgpu_synthesizer_set_phase.argtypes = [vp, i64]
     L.tsdgpu_synthesizer_out_count.argtypes = [vp, i64]
     L.tsdgpu_synthesizer_out_count.restype = i64
     L.tsdgpu_synthesizer_step.argtypes = [vp, vp, i64, i64, vp, i64, C.POINTER(i64), vp]
@@ -976,30 +982,46 @@ class Channelizer:
 
 
 class Synthesizer:
-    """Maximally decimated polyphase synthesis bank (tsdgpu_synthesizer), the dual of Channelizer: `channels` = M complex64 rows
-    into ONE stream, one launch per step.  step(u) takes the (M, F) block a Channelizer or a bank wrote and returns the F M
-    samples x[p] = sum_c exp(+2 pi i c p / M) sum_m u[c, m] f[p - m M]."""
+    """Polyphase synthesis bank (tsdgpu_synthesizer), the dual of Channelizer: `channels` = M complex64 rows into ONE stream, one
+    launch per step.  `oversample` = OS in {1, 2, 4}: a frame per hop of D = M / OS output samples (1: the maximally decimated
+    bank).  step(u) takes the (M, F) block a Channelizer of the same `oversample` or a bank wrote and returns the F D samples
+    x[p] = sum_c exp(+2 pi i c p / M) sum_m u[c, m] f[p - m D], p counted over the whole stream.  For OS > 1 the state is the
+    history and `phase`, the hops consumed so far modulo OS: move both to continue a stream in a fresh handle."""
 
-    def __init__(self, taps, channels):
+    def __init__(self, taps, channels, oversample=1):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        self.channels, self.K = int(channels), len(t)
+        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
         self._h = C.c_void_p()
-        _check(lib().tsdgpu_synthesizer_create(C.byref(self._h), self.channels, t.ctypes.data if len(t) else None, len(t)))
+        pt = t.ctypes.data if len(t) else None
+        if self.oversample == 1:
+            _check(lib().tsdgpu_synthesizer_create(C.byref(self._h), self.channels, pt, len(t)))
+        else:
+            _check(lib().tsdgpu_synthesizer_create_oversampled(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
         self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
-        self.frames_kept = self.history_len // self.channels            # P - 1
+        self.frames_kept = self.history_len // self.channels            # P - 1 (OS > 1: Q - 1, Q = ceil(K / D))
+        self.hop = lib().tsdgpu_synthesizer_hop(self._h)
+
+    @property
+    def phase(self):
+        """hops consumed so far, modulo `oversample`"""
+        return lib().tsdgpu_synthesizer_get_phase(self._h)
+
+    @phase.setter
+    def phase(self, hops):
+        _check(lib().tsdgpu_synthesizer_set_phase(self._h, int(hops)))
 
     def out_count(self, frames):
         return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
 
     def step(self, u, x=None, stream=None):
         """u: (M, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
-        x: 1-D with at least F M samples, of u's kind (default: a new one); returns its first F M samples."""
+        x: 1-D with at least F D samples, of u's kind (default: a new one); returns its first F D samples."""
         if _dtype_code(u) != C64 or u.ndim != 2:
             raise TsdGpuError("the synthesizer takes a 2-D (channels, frames) complex64 block")
         pu, ldu = _ptr2d(u, self.channels)
         F = int(u.shape[1])
         if x is None:
-            x = np.empty(F * self.channels, u.dtype) if isinstance(u, np.ndarray) else u.new_empty(F * self.channels)
+            x = np.empty(F * self.hop, u.dtype) if isinstance(u, np.ndarray) else u.new_empty(F * self.hop)
         if _dtype_code(x) != C64 or x.ndim != 1:
             raise TsdGpuError("the synthesizer writes a 1-D complex64 stream")
         got = C.c_int64(0)

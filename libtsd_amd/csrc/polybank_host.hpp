@@ -1,4 +1,5 @@
-// polybank_host.hpp -- the host side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip): what a
+// polybank_host.hpp -- the host side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip,
+// synthesizer_os.hip): what a
 // handle holds, its tables and history, the geometry of a launch, and the map from M to the kernels' <R0, NPOS>.  The entry
 // points, their argument checks and their messages stay with each operator.
 #pragma once
@@ -29,16 +30,16 @@ struct PolyBank {
 
 inline size_t hist_bytes(const PolyBank *c) { return (size_t) c->HW * sizeof(cpx); }
 
-// Fills a new handle: the shape (P = ceil(K / M) rows), the device's CUs, then one allocation and one upload: the P M taps, row p
+// Fills a new handle: the shape (P = `rows` tap rows of M; 0: ceil(K / M)), the device's CUs, then one allocation and one upload: the P M taps, row p
 // position s taking h[tap_index(p, s)] (zeros past K), then W_M^i, i < M / 16; and the zeroed double history of hist_len(P)
 // samples.  `who` heads the messages.  On an error the caller destroys the handle.
 template <typename HIST, typename INDEX>
-int polybank_init(PolyBank *c, const char *who, int M, const float *taps_host, int ntaps, HIST hist_len, INDEX tap_index)
+int polybank_init(PolyBank *c, const char *who, int M, const float *taps_host, int ntaps, HIST hist_len, INDEX tap_index, int rows = 0)
 {
   c->M = M;
   c->lgM = __builtin_ctz((unsigned) M);
   c->K = ntaps;
-  c->P = (ntaps + M - 1) / M;
+  c->P = rows ? rows : (ntaps + M - 1) / M;
   c->HW = hist_len(c->P);
   c->FP = chan_frame_pitch(M);
   int dev = 0;

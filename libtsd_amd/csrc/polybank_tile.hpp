@@ -1,4 +1,5 @@
-// polybank_tile.hpp -- the device side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip): a
+// polybank_tile.hpp -- the device side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip,
+// synthesizer_os.hip): a
 // workgroup of CHAN_NT threads, R = CHAN_NT / M sub-runs of 16-frame units, one LDS image of 16 R frames at pitch FP
 // (channelizer_internal.hpp).  Here are the thread's place in that tile, the channel-major read-back of the two analysis banks,
 // and the register window of a position with its fma chains.  Where a bank's samples come from and where its frames go stays in

@@ -19,13 +19,12 @@
 // The P - 1 halo frames are loaded and transformed only where a sub-run starts (one unit more per sub-run, nothing stored): from
 // the handle's history when they lie before the step.  The last workgroup writes the new history (the last P - 1 input frames of
 // old history ++ u, per channel) into the other buffer.
+// The oversampled bank (hop D = M / OS, OS in {2, 4}) is the sibling kernel of synthesizer_os.hip; the handle and the entry points
+// below serve both.
 #include "common.hpp"
 #include "bank_internal.hpp"
-#include "polybank_host.hpp"
+#include "synthesizer_handle.hpp"
 #include "polybank_tile.hpp"
-
-// d_tab: f[j][s] = f[j M + s]; HW = (P - 1) M history samples as an (M, P - 1) block: row c channel c's last P - 1 inputs, oldest first
-struct tsdgpu_synthesizer : tsdgpu::PolyBank {};
 
 namespace tsdgpu {
 namespace {
@@ -180,21 +179,37 @@ extern "C" {
 
 int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps)
 {
+  return tsdgpu_synthesizer_create_oversampled(out, channels, 1, taps_host, ntaps);
+}
+
+int tsdgpu_synthesizer_create_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
   TSD_CHECK(out != nullptr, "synthesizer_create: out is NULL");
   *out = nullptr;
   TSD_CHECK(channels >= 1, "synthesizer_create: channels = %d, need at least one", channels);
+  TSD_CHECK(oversample >= 1, "synthesizer_create: oversample = %d, need at least one", oversample);
   TSD_CHECK(taps_host != nullptr && ntaps >= 1, "synthesizer_create: K > 0 taps required");
   if (!chan_served_channels(channels))
     return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: channels = %d: served are the powers of two from %d to %d", channels,
                    CHAN_MIN_M, CHAN_MAX_M);
-  if (ntaps > CHAN_MAX_P * channels)
+  if (!chan_served_oversample(oversample))
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: oversample = %d: served are 1, 2 and 4", oversample);
+  if (oversample == 1 && ntaps > CHAN_MAX_P * channels)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
                    ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
+  // K <= 16 D: Q <= 16, the register window of a position stays within 15 older frames
+  if (ntaps > CHAN_MAX_P * (channels / oversample))
+    return set_err(TSDGPU_ERR_UNSUPPORTED,
+                   "synthesizer_create: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)", ntaps, channels,
+                   channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
   tsdgpu_synthesizer *c = new tsdgpu_synthesizer();
-  const int M = channels;
-  // f[j][s] = f[j M + s]; the history is the last P - 1 input frames
+  const int M = channels, D = M / oversample;
+  c->OS = oversample;
+  c->D = D;
+  // Q = ceil(K / D) rows (OS = 1: P = ceil(K / M)), row j position r taking f[j D + (r mod D)] (OS = 1: f[j M + r]); the history is
+  // the last Q - 1 input frames
   const int rc = polybank_init(c, "synthesizer_create", M, taps_host, ntaps, [M](int P) { return (P - 1) * M; },
-                               [M](int p, int s) { return p * M + s; });
+                               [D](int p, int r) { return p * D + r % D; }, (ntaps + D - 1) / D);
   if (rc) {
     tsdgpu_synthesizer_destroy(c);
     return rc;
@@ -203,7 +218,7 @@ int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const floa
   return TSDGPU_OK;
 }
 
-int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *c, int64_t frames) { return (!c || frames < 0) ? -1 : frames * c->M; }
+int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *c, int64_t frames) { return (!c || frames < 0) ? -1 : frames * c->D; }
 
 int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, int64_t frames, void *x, int64_t x_capacity, int64_t *n_out,
                             void *stream)
@@ -212,7 +227,7 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   TSD_CHECK(frames >= 0, "synthesizer_step: negative frame count");
   if (n_out) *n_out = 0;
   if (frames == 0) return TSDGPU_OK;
-  const int64_t F = frames, n = F * c->M;
+  const int64_t F = frames, n = F * c->D;
   TSD_CHECK(u != nullptr && x != nullptr, "synthesizer_step: NULL buffer");
   TSD_CHECK(n <= x_capacity, "synthesizer_step: the output needs %lld samples, x_capacity is %lld", (long long) n, (long long) x_capacity);
   TSD_CHECK(ldu >= F, "synthesizer_step: ldu = %lld below the %lld inputs of a channel", (long long) ldu, (long long) F);
@@ -227,11 +242,13 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   int rc;
   if ((rc = bank_stage_in(u, ldu, F, c->M, sz, false, F, c->in_stage, st, &du, &dldu))) return rc;
   if ((rc = stage_out(x, (size_t) n * sz, c->out_stage, &dx, &staged))) return rc;
-  rc = polybank_radix(c->M, [&](auto r0, auto npos) {
+  if (c->OS > 1) rc = syn_os_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
+  else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
     return syn_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
   });
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
+  c->phase = (int) ((c->phase + F) % c->OS);
   if (n_out) *n_out = n;
   return finish_out(x, (size_t) n * sz, dx, staged, st);
 }
@@ -239,10 +256,24 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
 int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *c)
 {
   TSD_CHECK(c != nullptr, "synthesizer_reset: NULL handle");
-  return polybank_reset(c);
+  if (const int rc = polybank_reset(c)) return rc;
+  c->phase = 0;
+  return TSDGPU_OK;
 }
 
 int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *c) { return c ? c->HW : -1; }
+
+int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *c) { return c ? c->D : -1; }
+
+int tsdgpu_synthesizer_get_phase(const tsdgpu_synthesizer *c) { return c ? c->phase : -1; }
+
+int tsdgpu_synthesizer_set_phase(tsdgpu_synthesizer *c, int64_t hops)
+{
+  TSD_CHECK(c != nullptr, "synthesizer_set_phase: NULL handle");
+  TSD_CHECK(hops >= 0, "synthesizer_set_phase: %lld hops, a negative count", (long long) hops);
+  c->phase = (int) (hops % c->OS);
+  return TSDGPU_OK;
+}
 
 int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *c, void *hist_dst, void *stream)
 {

@@ -86,6 +86,12 @@ sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux, en
 // frame share one transform: the error bound is 1e-5 of the peak of the step, and a NaN / Inf in input frame m reaches every
 // sample of output frames m .. m + ceil(K / nb_canaux) - 1.  Served: nb_canaux a power of two in [8, 1024], K <= 16 nb_canaux.
 sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux);
+// The same bank oversampled by surech = OS in {1, 2, 4}, the way back from canaliseur_polyphase(h, nb_canaux, surech): a frame per
+// hop of D = nb_canaux / OS output samples.  step(x, y): x.rows() = nb_canaux blocks of F samples (else échec); y is resized to
+// D * F.  The object carries the history (the last ceil(K / D) - 1 frames) and the phase of the hop; a NaN / Inf in input frame m
+// reaches every sample of output hops m .. m + ceil(K / D) - 1.  Served: nb_canaux as above, K <= 16 D; else the factory fails.
+// surech = 1 is the factory above.
+sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux, entier surech);
 
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
