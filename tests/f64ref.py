@@ -229,14 +229,15 @@ def windows(edges, n, maxlen=2048):
     return np.unique(np.array(out))
 
 
-def burst_train(rng, n, wmax, cplx=False, loud=(1e4, 1e6), quiet=(1.0, 1e-3)):
+def burst_train(rng, n, wmax, cplx=False, loud=(1e4, 1e6), quiet=(1.0, 1e-3), lo=300, hi=None):
     """Seeded burst train: loud segments, quiet segments, exact-zero stretches, of random lengths between about 300
-    and 3 wmax.  -> (x float32/complex64, segment edges, kinds) with kinds in {"loud", "quiet", "zero"}."""
+    and 3 wmax (`lo`, `hi`: other limits, for streams too short for those).
+    -> (x float32/complex64, segment edges, kinds) with kinds in {"loud", "quiet", "zero"}."""
     edges, kinds, amps = [0], [], []
     o = 0
-    hi = max(600, 3 * int(wmax))
+    hi = max(600, 3 * int(wmax)) if hi is None else int(hi)
     while o < n:
-        L = int(rng.integers(300, hi))
+        L = int(rng.integers(lo, hi))
         r = rng.random()
         if r < 0.3:
             k, a = "loud", float(rng.choice(loud))

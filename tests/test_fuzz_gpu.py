@@ -377,3 +377,59 @@ def test_fuzz_detector(tg, orc, seed):
         _, pk = det.step(x[b * Ne:(b + 1) * Ne].copy())
         found += [b * Ne + p.index - det.delay for p in pk]
     assert found == starts, (seed, M, Ne, mode)
+
+
+# ---- round 3: the polyphase banks (channelizer / synthesizer, plain and oversampled), per frame against float64 -----------
+def _bank_stream(make, data, cut, steps, D, rows):
+    """the stream through a handle in `steps` (frame counts); at frame `cut` its state and phase move to a fresh handle, and both
+    go on: -> (the first handle's output, the two continuations)"""
+    import torch
+    part = (lambda a, b: data[:, a:b]) if rows else (lambda a, b: data[a * D:(b) * D])
+    first, fresh, outs, tail, o = make(), None, [], [], 0
+    for f in steps:
+        if o == cut:
+            fresh = make()
+            fresh.set_state(first.get_state())
+            fresh.phase = first.phase
+        y = first.step(part(o, o + f))
+        outs.append(y)
+        if fresh is not None:
+            tail.append((y, fresh.step(part(o, o + f))))
+        o += f
+    torch.cuda.synchronize()
+    cat = (lambda v: torch.cat(v)) if rows else (lambda v: torch.cat(v, dim=1))
+    return cat(outs).cpu().numpy(), cat([a for a, _ in tail]).cpu().numpy(), cat([b for _, b in tail]).cpu().numpy()
+
+
+@pytest.mark.parametrize("pair", ["plain", "oversampled"])
+@pytest.mark.parametrize("seed", range(40 * SCALE))
+def test_fuzz_polyphase_banks(tg, pair, seed):
+    """random (M, OS, K in [1, 16 D], frames, ragged steps) through the channelizer and the synthesizer of the pair: every frame /
+    sample inside its float64 bound (tests/poly_f64.py), and a hand-over of state + phase to a fresh handle at a random cut gives
+    the same bits"""
+    import torch
+    import poly_f64 as PF
+    rng = np.random.default_rng([10000, pair == "oversampled", seed])
+    M = int(rng.choice([8, 16, 32, 64, 128, 256, 512, 1024]))
+    OS = 1 if pair == "plain" else int(rng.choice([2, 4]))
+    D = M // OS
+    F = int(rng.integers(1, 401))
+    for bank in ("chan", "syn"):
+        K = int(rng.integers(1, 16 * D + 1))
+        h = PF.taps(rng, K)
+        steps = PF.ragged(rng, F)
+        cut = int(np.concatenate([[0], np.cumsum(steps)])[rng.integers(len(steps))])
+        what = (seed, bank, M, OS, K, F, cut)
+        if bank == "chan":
+            x = PF.chan_input(rng, F * D, M)
+            ref, bound = PF.chan(x, PF.chan_table(h, M), M, OS)
+            y, ya, yb = _bank_stream(lambda: tg.Channelizer(h, M, oversample=OS), torch.from_numpy(x).cuda(), cut, steps, D, False)
+            ratio = PF.chan_judge(y, ref, bound, what)
+        else:
+            u = PF.syn_input(rng, M, F)
+            ref, bound = PF.syn(u, PF.syn_table(h, D), M, OS)
+            y, ya, yb = _bank_stream(lambda: tg.Synthesizer(h, M, oversample=OS), torch.from_numpy(u).cuda(), cut, steps, D, True)
+            ratio = PF.syn_judge(y, ref, bound, what)
+        print(what, "worst err / bound", ratio)
+        assert ratio <= 1.0, what
+        assert np.array_equal(ya.view(np.uint32), yb.view(np.uint32)), what

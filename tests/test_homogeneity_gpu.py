@@ -38,12 +38,12 @@ def run(make, x, cuts=None):
     return np.concatenate(out)
 
 
-def check(make, x, cuts=None, power=1):
-    """Determinism, then y(2^k x) == 2^(power k) y(x) for k = +-60 (power 2 for quadratic outputs)."""
+def check(make, x, cuts=None, power=1, ks=KS):
+    """Determinism, then y(2^k x) == 2^(power k) y(x) for k in ks (+-60; power 2 for quadratic outputs)."""
     y = run(make, x, cuts)
     assert np.array_equal(run(make, x, cuts), y, equal_nan=True), "two runs differ"
     assert np.isfinite(y).all()
-    for k in KS:
+    for k in ks:
         s = np.float32(2.0 ** k)
         ys = run(make, (x * s).astype(x.dtype), cuts)
         want = (y * np.float32(2.0 ** (power * k))).astype(y.dtype)
@@ -183,3 +183,35 @@ def test_sharded_sos(tg, orc):
             import torch
             return torch.from_numpy(self.s.step_host(xd.cpu().numpy()))
     check(_S, x, [(0, 300001), (300001, 1 << 20)])
+
+
+class _Syn:
+    """the synthesizer over a frame-major stream: M samples = one frame of the (M, F) block"""
+    def __init__(self, tg, f, M, OS):
+        self.s, self.M = tg.Synthesizer(f, M, oversample=OS), M
+
+    def step(self, x):
+        return self.s.step(x.view(-1, self.M).t().contiguous())
+
+
+@pytest.mark.parametrize("bank", ["chan", "syn"])
+@pytest.mark.parametrize("M,OS,K", [(8, 1, 5 * 8), (64, 1, 4 * 64 - 3), (1024, 1, 3 * 1024 + 1), (16, 4, 13 * 4), (64, 2, 11 * 32 - 5),
+                                    (1024, 2, 1025)])
+def test_polyphase_banks(tg, bank, M, OS, K):
+    """The four banks (channelizer / synthesizer, plain and oversampled), k in {-20, 7, 30}.  |x| ~ 1 and taps ~ 1/4: at k = 30 a
+    product is ~ 1e9 and an output sums at most 16 M <= 2^14 of them, far below 2^128; at k = -20 a product of two small normal
+    draws (1e-5 each, say) is 1e-16, far above 2^-126: nothing overflows or goes subnormal.  Ragged steps of odd frame counts:
+    the phase of the oversampled banks moves."""
+    f = rand(K, False, M + OS) * np.float32(0.25)
+    D = M // OS
+    frames = [0, 1, 18, 33, 150]
+    per = D if bank == "chan" else M
+    make = (lambda: tg.Channelizer(f, M, oversample=OS)) if bank == "chan" else (lambda: _Syn(tg, f, M, OS))
+
+    class _Flat:
+        def __init__(self):
+            self.op = make()
+
+        def step(self, x):
+            return self.op.step(x).reshape(-1)
+    check(_Flat, rand(150 * per, True, K), [(a * per, b * per) for a, b in zip(frames[:-1], frames[1:])], ks=(-20, 7, 30))
