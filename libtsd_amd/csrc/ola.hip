@@ -878,7 +878,10 @@ __global__ void spec_finish_kernel(const float *__restrict__ part, const float *
           }
         m = m / scale;
         if (F.sweep) m = m / mag_cnt[idx];
-        y[(size_t) g * F.Ns + idx] = 10.f * log10f(m + 1.17549435e-38f);        // pow2db(mag_moy + numeric_limits<float>::min())
+        // pow2db(mag_moy + numeric_limits<float>::min()).  The logarithm is taken in double and rounded once: the device's log10f is up
+        // to 2 ulp off, the reference's std::log10(float) within one -- scaling the input by 2^k moved a row by 2.3 ulp more than
+        // 10 log10(4^k) (tests/test_homogeneity_gpu.py::test_spectrum), and a sum of exactly zero did not read 10 log10(FLT_MIN)
+        y[(size_t) g * F.Ns + idx] = 10.f * (float) log10((double) (m + 1.17549435e-38f));
       }
       if (last && idx < F.Nf)
         for (int c = 0; c < ncls; c++) acc_out[(size_t) c * F.Nf + idx] = 0.f;    // mag_moy.setZero()

@@ -12,7 +12,7 @@ run() {   # run "ENV=1 [ENV2=..]" files...
 FAILED=0
 run TSDGPU_FFT_GENERIC=1 tests/test_fft_gpu.py tests/test_ola_gpu.py
 run TSDGPU_FFT_NO_SMOOTH=1 tests/test_fft_gpu.py
-run TSDGPU_OLA_UNFUSED=1 tests/test_ola_gpu.py tests/test_detect_gpu.py
+run TSDGPU_OLA_UNFUSED=1 tests/test_ola_gpu.py tests/test_detect_gpu.py tests/test_spectral_dynamic_range_gpu.py
 run TSDGPU_RFFT_TWO_PASS=1 tests/test_fft_gpu.py
 run TSDGPU_POLY_COMPOSED=1 tests/test_polyphase_gpu.py -k "not direct_kernel"      # (that test asserts the bits of the fused / direct kernels)
 run TSDGPU_POLY_NO_ROWS=1 tests/test_polyphase_gpu.py tests/test_host_pipeline_gpu.py

@@ -216,3 +216,250 @@ def test_error_measures():
     assert list(R.windows([0, 5000, 6000], 7000)) == [0, 2048, 4096, 5000, 6000, 7000]
     x, edges, kinds = R.burst_train(np.random.default_rng(1), 100000, 1000)
     assert edges[-1] == 100000 and {"loud", "quiet", "zero"} <= set(kinds)
+
+
+# ---- the spectral estimators, the correlations and the detector (tests/test_spectral_dynamic_range_gpu.py's references):
+# each reference against the oracle on white noise, then each bound "on the reference alone" -- (a) libtsd's float32
+# statements (the oracle) stay inside it on the inputs of the GPU tests, (b) a planted defect does not
+def _oo():
+    from oracle import ola_oracle
+    return ola_oracle
+
+
+def _G():
+    import test_spectral_dynamic_range_gpu as G
+    return G
+
+
+@pytest.mark.parametrize("N", [64, 100, 1024])
+def test_welch_parts(orc, N):
+    x = rand(30 * N + 3, True, N)
+    w = _oo().fen_hann_periodique(N)
+    S, k = _oo().psd_welch_sum(x, N, w)
+    P, B, k2 = R.welch_parts(x, N, w)
+    ref, k3 = R.welch_sum(x, N, w)
+    assert k == k2 == k3 and relerr(S, P) <= 2e-5 and relerr(P, ref) <= 1e-12
+    assert (B > 0).all()
+
+
+@pytest.mark.parametrize("down", [60, 100])
+@pytest.mark.parametrize("N", [64, 1024, 4096, 1000])
+def test_welch_bound_holds_for_the_oracle_and_catches_a_dropped_segment(orc, N, down):
+    w = _oo().fen_hann_periodique(N)
+    x = R.two_tone(N, 40 * N + 3, down)
+    P, B, nseg = R.welch_parts(x, N, w)
+    S, k = _oo().psd_welch_sum(x, N, w)
+    assert k == nseg == 79
+    ratio = float((np.abs(S - P) / B).max())
+    print("welch oracle / bound", N, down, ratio)
+    assert ratio <= (0.05 if N != 1000 else 0.6)              # (a): room to spare (1000: the float32-chirp Bluestein)
+    kw = N // 2 + N // 3 + 1                                   # the weak line, fftshift-ed
+    assert B[kw] <= 2e-3 * 1e-5 * P.max()                      # ... and the bound there is 500 times (at -100 dB 1e5 times) inside today's 1e-5 of the peak
+    # (b) one segment dropped: 1/79 of every line is missing -- outside the bound on the strong line (on the weak one the
+    # transform's own share of the bound is 1/85 of the line at -60 dB and 0.7 of it at -100 dB: float32 resolves no better)
+    S2, k2 = _oo().psd_welch_sum(x[:-(N // 2)], N, w)
+    ks = N // 2 + N // 8
+    assert k2 == nseg - 1 and np.abs(S2 - P)[ks] > 100 * B[ks]
+
+
+class _LeakySpectrum:
+    """The oracle's Spectrum whose completed group leaves 2^-20 of its sums in the accumulator."""
+    def __init__(self, *a, **k):
+        self.o = _oo().Spectrum(*a, **k)
+
+    def step(self, x):
+        o = self.o
+        if o.cntmag + 1 < o.nmeans:
+            return o.step(x)
+        nm, o.nmeans = o.nmeans, 1 << 30
+        o.step(x)                                              # accumulates only
+        o.nmeans, o.cntmag = nm, nm - 1
+        acc = o.mag_moy.copy()
+        y = o.step(np.zeros(o.BS, np.complex64))               # adds exact zeros, completes the group
+        o.mag_moy += acc * np.float32(2.0 ** -20)
+        return y
+
+
+def _spectrum_case(BS, nsubs, nmeans, sweep, make=None):
+    oo = _oo()
+    Nf = BS // nsubs
+    w = oo.fen_hann_periodique(Nf)
+    ref = oo.Spectrum(BS, nmeans, nsubs, w, sweep=sweep)
+    run = ref if make is None else make(BS, nmeans, nsubs, w, sweep=sweep)
+    x = R.spectrum_train(BS, nmeans, BS + nsubs)
+    rows = [run.step(x[b * BS:(b + 1) * BS]) for b in range(len(x) // BS)]
+    y = np.stack([v for v in rows if len(v)])
+    P, B = R.spectrum(x, BS, nsubs, nmeans, ref.f, None if sweep is None else sweep[0], ref.masque, getattr(ref, "mag_cnt", None))
+    return y, P, B
+
+
+def test_spectrum_matches_oracle_on_white_noise(orc):
+    oo = _oo()
+    for BS, nsubs, nmeans, sweep in [(1024, 1, 3, None), (4096, 4, 2, (700, 3, 20)), (4099, 4, 2, None), (1024, 1, 2, (300, 2, 20))]:
+        Nf = BS // nsubs
+        ref = oo.Spectrum(BS, nmeans, nsubs, oo.fen_hann_periodique(Nf), sweep=sweep)
+        x = rand(2 * nmeans * BS, True, BS)
+        y = np.stack([v for v in (ref.step(x[b * BS:(b + 1) * BS]) for b in range(2 * nmeans)) if len(v)])
+        P, _ = R.spectrum(x, BS, nsubs, nmeans, ref.f, None if sweep is None else sweep[0], ref.masque, getattr(ref, "mag_cnt", None))
+        assert P.shape == y.shape
+        lin, _ = R.db_to_linear(y)
+        assert relerr(lin, P) <= TOL
+        assert np.array_equal(P == 0, y == y.min()) or (P > 0).all()
+
+
+def test_spectrum_bound_holds_for_the_oracle_and_catches_a_leak(orc):
+    floor = np.float32(10) * np.log10(np.float32(R.FLT_MIN), dtype=np.float32)
+    for BS, nsubs, nmeans, sweep in _G().SPEC_SHAPES:
+        y, P, B = _spectrum_case(BS, nsubs, nmeans, sweep)
+        lin, lg = R.db_to_linear(y)
+        ratio = float((np.abs(lin - P) / np.maximum(B + lg, 1e-300)).max())
+        print("spectrum oracle / bound", BS, nsubs, nmeans, sweep, ratio, "rows dB", y.max(axis=1).round(1))
+        assert ratio <= 0.5                                    # (a)
+        assert (y[[2, 7]] == floor).all() and (y[P == 0] == floor).all()
+        # (b) 2^-20 of a loud group's sums left behind: the quiet row after it is outside its bound
+        yl, _, _ = _spectrum_case(BS, nsubs, nmeans, sweep, make=_LeakySpectrum)
+        linl, lgl = R.db_to_linear(yl)
+        bad = np.abs(linl - P) > B + lgl
+        assert bad[1].any() and bad[7].any() and not bad[0].any()
+
+
+@pytest.mark.parametrize("n,m", [(64, -1), (1000, 10), (777, 300), (512, 512)])
+def test_xcorr(orc, n, m):
+    oo = _oo()
+    x, y = rand(n, True, 1), rand(n, True, 2)
+    mm = n if m < 0 else m
+    c = np.correlate(x.astype(np.complex128), y.astype(np.complex128), "full")
+    want = c[::-1][n - 1 - (mm - 1): n - 1 + mm] / n
+    assert np.abs(R.xcorr(x, y, m) - want).max() <= 1e-12
+    L = n + 2 * mm
+    tol = TOL if L & (L - 1) == 0 else 1.5e-3                  # (the oracle's float32-chirp Bluestein off the powers of two, as in test_fft)
+    assert relerr(oo.xcorrb(x, y, m)[1], R.xcorr(x, y, m)) <= tol
+    assert relerr(oo.xcorrb(x, None, m)[1], R.xcorr(x, None, m)) <= tol
+    w = R.xcorr_weights(n, mm)
+    assert np.abs(oo.xcorr(x, y, m)[1] - R.xcorr(x, y, m, True)).max() <= tol * np.abs(want).max() / w.min()
+
+
+@pytest.mark.parametrize("kind", ["white", "half80", "quietloud"])
+@pytest.mark.parametrize("n,m", [(1024, 512), (3072, 512), (65336, 100)])
+def test_xcorr_flat_bound_at_power_of_two_sizes(orc, n, m, kind):
+    """L = n + 2m a power of two: the oracle's radix-2 plan is within 3 C_FFT u log2(L) ||x|| ||y|| / n of the definition
+    (two forward transforms and the inverse one, each normwise; ||X|| = ||x|| for the unitary transform)."""
+    L = n + 2 * m
+    assert L & (L - 1) == 0
+    x, y = _G().xcorr_inputs(n, kind)
+    r = _oo().xcorrb(x, y, m)[1]
+    flat = _G().xcorr_flat_bound(x, y, n, m)
+    e = np.abs(r - R.xcorr(x, y, m)).max()
+    print("xcorr oracle / flat bound", n, m, kind, e / flat)
+    assert e <= flat
+    assert np.abs(np.roll(r, 1) - R.xcorr(x, y, m)).max() > flat          # lags off by one are outside it
+
+
+def _det_emulation(orc, pu, x, late=0):
+    """libtsd's float32 statements of the FIR-mode detector: FiltreRIF with the conjugated reversed pattern, the M-tap
+    moving average of |x|^2 (late: that average taken `late` samples late), the score."""
+    M = len(pu)
+    c = orc.fir(np.conj(pu[::-1]).astype(np.complex64), x)
+    a2 = (x.real * x.real + x.imag * x.imag).astype(np.float32)
+    e = orc.fir(np.full(M, np.float32(1.0 / M), np.float32), a2)
+    if late:
+        e = np.concatenate([np.zeros(late, np.float32), e[:-late]])
+    m2 = (c.real * c.real + c.imag * c.imag).astype(np.float32)
+    m2 = np.where(m2 <= np.float32(1e-12), np.float32(0), m2)
+    return (np.float32(1.0 / np.sqrt(np.float32(M))) * np.sqrt(m2 / (e + np.float32(1e-20)))).astype(np.float32)
+
+
+@pytest.mark.parametrize("M", [31, 200, 513])
+def test_detector_bound_holds_for_a_float32_run_and_catches_a_late_energy(orc, M):
+    G = _G()
+    pat, x, edges, kinds, starts = R.detector_stream(G.DET_SEED + M, M)
+    pu = R.unit_pattern(pat)
+    d = R.detector(pu, x, 1, threshold=G.DET_THRESHOLD)
+    keep = G.det_keep(d)
+    assert 1 - keep.mean() <= 1e-3                              # the leave-out share of the GPU test's seeds
+    s32 = _det_emulation(orc, pu, x)
+    ratio = np.abs(s32 - d["s"]) / np.maximum(d["bound"], 1e-300)
+    print("detector M", M, "float32 run / bound", float(ratio[keep].max()), "left out", float(1 - keep.mean()),
+          "peaks", len(d["peaks"]), "certain", int((d["margins"] > 2 * d["local"]).sum()))
+    assert ratio[keep].max() <= 0.5
+    assert (d["margins"] > 2 * d["local"]).sum() >= 20          # the planted patterns give peaks the test can insist on
+    late = _det_emulation(orc, pu, x, late=1)
+    assert (np.abs(late - d["s"])[keep] > d["bound"][keep]).any()
+    # and on white noise the scores agree with the float32 run at the file's tolerance
+    xw = rand(20000, True, M)
+    dw = R.detector(pu, xw, 1)
+    assert relerr(_det_emulation(orc, pu, xw), dw["s"]) <= TOL
+
+
+def test_detector_ola_mode_is_the_fir_mode_delayed(orc):
+    pat, x, _, _, _ = R.detector_stream(5, 31, n=1 << 14)
+    pu = R.unit_pattern(pat)
+    a, b = R.detector(pu, x, 1, threshold=0.7), R.detector(pu, x, 1024, Ne=512, threshold=0.7)
+    D = 512 - 30
+    keep = (a["m2"][:-D] > 4e-12 * 1024)
+    assert np.abs(b["s"][D:] - a["s"][:-D])[keep].max() <= 1e-12 * (1 + a["s"].max()) and (b["s"][:D] == 0).all()
+    assert list(b["peaks"]) == [i + D for i in a["peaks"] if i + D <= len(x) - 31]
+    # the engine's own float32 run (the oracle's OLA with the oracle's transform of the pattern) is inside the bound
+    oo = _oo()
+    p2 = np.zeros(1024, np.complex64)
+    p2[:31] = pu
+    H = np.conj(orc.fft(p2, True))
+    c = oo.Ola(512, 30, None, lambda X: X * H).step(x)
+    cb = b["cb"]
+    assert (np.abs(c - np.where(b["m2"] <= 1e-12, c, b["c"])) <= cb + 1e-30).all()
+
+
+def _ola_w_float32(Ne, nz, win, H, x, defect=False):
+    """ola_oracle.Ola's windowed branch; defect: `last`'s second half is not cleared (fourier.cc:902 left out)."""
+    oo = _oo()
+    o = oo.Ola(Ne, nz, win, lambda X: X * H)
+    if not defect:
+        return o.step(x)
+    N, Nz, h = o.N, o.Nz, Ne // 2
+    fc = o.fen.astype(np.complex64)
+    out = []
+    for b in range(len(x) // Ne):
+        xb = x[b * Ne:(b + 1) * Ne]
+        o.padded[N - h:] = xb[:h]
+        o.padded[N - Ne:] *= fc
+        x2 = o._tf(o.padded)
+        o.svg[Ne - Nz:] += x2[:Nz]
+        o.last[h:] += o.svg[:h] / np.float32(2)
+        if b > 0:
+            out.append(o.last.copy())
+        o.last[:h] = o.svg[h:] / np.float32(2)                 # (o.last[h:] = 0 is the statement left out)
+        o.svg = x2[N - Ne:].copy()
+        o.padded[N - Ne:] = xb * fc
+        x2 = o._tf(o.padded)
+        o.svg[Ne - Nz:] += x2[:Nz]
+        o.last += o.svg / np.float32(2)
+        o.svg = x2[Nz:Nz + Ne].copy()
+        o.padded[Nz:Nz + h] = xb[h:]
+    return np.concatenate(out)
+
+
+@pytest.mark.parametrize("Ne,nz", [(512, 127), (64, 64), (1000, 24), (4096, 0)])
+def test_ola_windowed(orc, Ne, nz):
+    G = _G()
+    win = _oo().fen_hann_periodique(Ne)
+    N = orc.next_pow2(Ne + nz)
+    H = G.ola_response(orc, N)
+    xw = rand(12 * Ne + 17, True, Ne)
+    ref = R.ola_windowed(xw, Ne, N, H, win)
+    yo = _ola_w_float32(Ne, nz, win, H, xw)
+    assert len(ref) == len(yo) == 11 * Ne and relerr(yo, ref) <= TOL
+    assert relerr(_ola_w_float32(Ne, nz, win, H, xw, defect=False), _ola_w_float32(Ne, nz, win, H, xw)) == 0
+    # the bound on the GPU test's burst train: (a) the oracle inside, (b) `last` not cleared outside
+    x = G.ola_w_input(Ne, N)
+    ref = R.ola_windowed(x, Ne, N, H, win)
+    bound = G.ola_w_bound(x, N, H, win)[: len(ref)]
+    e = np.abs(_ola_w_float32(Ne, nz, win, H, x) - ref)
+    print("windowed ola oracle / bound", Ne, nz, float((e / np.maximum(bound, 1e-300)).max()))
+    assert (e <= 0.5 * bound).all()
+    assert (np.abs(_ola_w_float32(Ne, nz, win, H, x, defect=True) - ref) > bound).any()
+
+
+@pytest.mark.parametrize("n", [16, 1024, 1000, 6144])
+def test_rfft(orc, n):
+    x = rand(n, False, n)
+    assert relerr(orc.rfft(x), R.rfft(x)) <= (TOL if n & (n - 1) == 0 else 1.5e-3)

@@ -166,6 +166,40 @@ def test_welch(tg, N):
         assert np.array_equal(go((x * np.float32(2.0 ** k)).astype(np.complex64)), (y * np.float32(2.0 ** (2 * k))).astype(np.float32)), k
 
 
+@pytest.mark.parametrize("n,m", [(1024, 512), (1000, 300)])
+def test_xcorr(tg, n, m):
+    """Biased cross-correlation, L = n + 2m a power of two (2048) and not (1600): bilinear, so 2^k on EITHER input scales
+    every lag by exactly 2^k."""
+    x, y = rand(n, True, n), rand(n, True, n + 1)
+    r = tg.xcorr(x, y, m, False)
+    assert np.array_equal(tg.xcorr(x, y, m, False), r) and np.isfinite(r).all()
+    for k in KS:
+        s = np.float32(2.0 ** k)
+        want = (r * s).astype(np.complex64)
+        assert np.array_equal(tg.xcorr((x * s).astype(np.complex64), y, m, False), want), ("x", k)
+        assert np.array_equal(tg.xcorr(x, (y * s).astype(np.complex64), m, False), want), ("y", k)
+
+
+@pytest.mark.parametrize("BS,nsubs,nmeans,sweep", [(1024, 1, 3, None), (4096, 4, 2, None), (4096, 4, 2, (700, 3, 20)), (3000, 3, 2, None)])
+def test_spectrum(tg, BS, nsubs, nmeans, sweep):
+    """The sums of |X|^2 scale exactly with 4^k; the row is 10 log10f of them, so it moves by the float32 10 log10 of 4^k:
+    within 2 ulp of the dB value (the two float32 logarithms).  |x| ~ 1 and k = +-10: FLT_MIN stays far below every bin."""
+    from oracle import ola_oracle
+    ref = ola_oracle.Spectrum(BS, nmeans, nsubs, ola_oracle.fen_hann_periodique(BS // nsubs), sweep=sweep)
+    make = lambda: tg.Spectrum(BS, nsubs, nmeans, ref.f, sweep=None if sweep is None else (sweep[0], ref.masque))
+    x = rand(2 * nmeans * BS, True, BS)
+    y = make().step(x)
+    assert np.array_equal(make().step(x), y) and y.shape[0] == 2
+    live = y > -300                                              # (bins the sweep leaves unreached read 10 log10(FLT_MIN) at every k)
+    for k in (10, -10):
+        ys = make().step((x * np.float32(2.0 ** k)).astype(np.complex64))
+        assert np.array_equal(ys[~live], y[~live])
+        want = y.astype(np.float64) + 10 * np.log10(4.0) * k
+        ulp = np.maximum(np.spacing(np.abs(ys)), np.spacing(np.abs(y))).astype(np.float64)
+        bad = np.abs(ys.astype(np.float64) - want)[live] > 2 * ulp[live]
+        assert not bad.any(), (k, int(bad.sum()), float((np.abs(ys - want) / ulp)[live].max()))
+
+
 def test_sharded_sos(tg, orc):
     """The sharded SOS over every device present (several shards per device when there is one)."""
     z, p, mn, md = orc.design_butter_lp(12, 0.25)
