@@ -391,11 +391,35 @@ int tsdgpu_polyfir_bank_destroy(tsdgpu_polyfir_bank *b);
  *  - non-finite inputs: a NaN / Inf at stream position q makes ALL channels of output frames
  *    floor(q / D) .. floor((q + P M) / D) - 1 non-finite (P OS frames) and nothing else.
  *  - chunk invariance, layouts, alignment and the error bound are those above.
+ *
+ * Real-input bank (tsdgpu_channelizer_create_real): ONE float32 stream into M / 2 + 1 complex64
+ * rows, the definition above for a real x and c = 0 .. M / 2.  Rows M / 2 + 1 .. M - 1 are the
+ * conjugates of rows M / 2 - 1 .. 1 and are not produced.  M is the transform length, as in
+ * tsdgpu_channelizer_create: the same prototype serves both.  What changes for a real handle
+ * (tsdgpu_channelizer_is_real() = 1):
+ *  - a step takes n = F*M FLOATS of x and writes F complex64 outputs to each of the
+ *    tsdgpu_channelizer_rows() = M / 2 + 1 rows y + c*ldy; the overlap check is against 4-B
+ *    inputs and M / 2 + 1 rows.  x needs only 4-B alignment (an 8-B aligned x takes wider
+ *    loads; the bits are the same); the rows are as above.
+ *  - rows 0 and M / 2 are written with an imaginary part of exactly 0 (finite inputs).
+ *  - state: the last tsdgpu_channelizer_history_len() = (P - 1) M input FLOATS, oldest first.
+ *  - a frame has a transform of its own (of M / 2 points): its bits do not depend on its
+ *    neighbours or on where the steps were cut, and x scaled by a power of two gives y scaled
+ *    by it, bit for bit (no overflow / underflow).
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [16, 1024], K <= 16 M, `oversample` = 1 (the argument is there for the oversampled real
+ *    bank, which is not served).  oversample < 1 is TSDGPU_ERR_INVALID.
+ *  - hop, out_count, reset, get_state / set_state, get_phase / set_phase (always 0) and destroy
+ *    serve the handle; chunk invariance, the error bound and the non-finite horizon are those
+ *    of the complex bank at OS = 1.
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_channelizer tsdgpu_channelizer;
 int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps);
 int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host,
                                           int ntaps);
+int tsdgpu_channelizer_create_real(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps);
+int tsdgpu_channelizer_rows(const tsdgpu_channelizer *c);                       /* channels / 2 + 1 (real), channels */
+int tsdgpu_channelizer_is_real(const tsdgpu_channelizer *c);                    /* 1: a float32 stream; 0: complex64 */
 int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c);                        /* D = channels / oversample */
 int tsdgpu_channelizer_get_phase(const tsdgpu_channelizer *c);                  /* hops consumed, modulo OS */
 int tsdgpu_channelizer_set_phase(tsdgpu_channelizer *c, int64_t hops);          /* taken modulo OS */

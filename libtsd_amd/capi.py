@@ -96,6 +96,11 @@ def _declare(L):
     L.tsdgpu_polyfir_bank_destroy.argtypes = [vp]
     L.tsdgpu_channelizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
     L.tsdgpu_channelizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_channelizer_create_real.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_channelizer_rows.argtypes = [vp]
+    L.tsdgpu_channelizer_rows.restype = i32
+    L.tsdgpu_channelizer_is_real.argtypes = [vp]
+    L.tsdgpu_channelizer_is_real.restype = i32
     L.tsdgpu_channelizer_hop.argtypes = [vp]
     L.tsdgpu_channelizer_hop.restype = i32
     L.tsdgpu_channelizer_get_phase.argtypes = [vp]
@@ -966,6 +971,76 @@ class Channelizer:
     def set_state(self, hist=None, stream=None):
         if self.history_len:
             assert tuple(hist.shape) == (self.history_len,) and _dtype_code(hist) == C64
+        _check(lib().tsdgpu_channelizer_set_state(self._h, _ptr(hist) if self.history_len else None,
+                                                  _stream_of(hist, stream) if self.history_len else stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_channelizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RealChannelizer:
+    """Polyphase analysis bank for a REAL stream (tsdgpu_channelizer_create_real): ONE float32 stream into `rows` = M / 2 + 1
+    complex64 rows, one launch per step.  step(x) takes n = F M floats and returns the (M / 2 + 1, F) block
+    y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m M + M - 1, c <= M / 2: the rows of Channelizer(taps, M) on
+    the widened stream that are not the conjugates of others (row M - c = conj row c), in the (C, n) layout the banks read.
+    The state is the last history_len = (P - 1) M floats."""
+
+    def __init__(self, taps, channels, oversample=1):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
+        self._h = C.c_void_p()
+        pt = t.ctypes.data if len(t) else None
+        _check(lib().tsdgpu_channelizer_create_real(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
+        self.rows = lib().tsdgpu_channelizer_rows(self._h)
+        self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
+        self.hop = lib().tsdgpu_channelizer_hop(self._h)
+
+    def out_count(self, n):
+        return lib().tsdgpu_channelizer_out_count(self._h, int(n))
+
+    def step(self, x, y=None, stream=None):
+        """x: 1-D float32 numpy array (host) or torch tensor (host or device), a whole number of frames of M samples.
+        y: (rows, m) complex64 with m >= n / M, of x's kind, rows may be strided (default: a new packed one); returns its
+        (rows, n / M) view."""
+        if _dtype_code(x) != F32 or x.ndim != 1:
+            raise TsdGpuError("the real-input channelizer takes a 1-D float32 stream")
+        n = int(x.shape[0])
+        if y is None:
+            nout = n // self.hop
+            if isinstance(x, np.ndarray):
+                y = np.empty((self.rows, nout), np.complex64)
+            else:
+                import torch
+                y = x.new_empty((self.rows, nout), dtype=torch.complex64)
+        if _dtype_code(y) != C64:
+            raise TsdGpuError("the real-input channelizer writes complex64 rows")
+        py, ldy = _ptr2d(y, self.rows)
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_channelizer_step(self._h, _ptr(x), n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
+        return y[:, : got.value]
+
+    def reset(self):
+        _check(lib().tsdgpu_channelizer_reset(self._h))
+
+    def get_state(self, dst=None, stream=None):
+        """the last history_len = (P - 1) M input floats, oldest first.  dst: packed float32 numpy array or torch tensor."""
+        if dst is None:
+            dst = np.zeros(self.history_len, np.float32)
+        assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == F32
+        _check(lib().tsdgpu_channelizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
+        return dst
+
+    def set_state(self, hist=None, stream=None):
+        if self.history_len:
+            assert tuple(hist.shape) == (self.history_len,) and _dtype_code(hist) == F32
         _check(lib().tsdgpu_channelizer_set_state(self._h, _ptr(hist) if self.history_len else None,
                                                   _stream_of(hist, stream) if self.history_len else stream))
 

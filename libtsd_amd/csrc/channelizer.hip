@@ -17,7 +17,8 @@
 //  - store: the bins are read back channel-major; a (channel, sub-run) pair receives its 16 frames as one 128-B segment.
 // The last workgroup writes the new history (the last (P - 1) M samples of old history ++ x) into the other buffer.
 // The handle also serves the oversampled bank (hop D = M / OS, OS in {2, 4}): its kernel family is channelizer_os.hip, and the
-// entry points below count a step in hops of D samples; at OS = 1 they are what they were.
+// entry points below count a step in hops of D samples; at OS = 1 they are what they were.  And the real-input bank
+// (channelizer_real.hip: a float32 stream into M / 2 + 1 rows): n and the history count floats there.
 // Shared with channelizer_os.hip and synthesizer.hip: polybank_tile.hpp (device; it says why the transform block is not in it) and
 // polybank_host.hpp (the handle: what it holds, how it is filled, launched and moved).
 #include "common.hpp"
@@ -207,8 +208,9 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   TSD_CHECK(x != nullptr && y != nullptr, "channelizer_step: NULL buffer");
   TSD_CHECK(F <= y_capacity, "channelizer_step: a channel's output needs %lld samples, y_capacity is %lld", (long long) F, (long long) y_capacity);
   TSD_CHECK(ldy >= F, "channelizer_step: ldy = %lld below the %lld outputs of a channel", (long long) ldy, (long long) F);
-  const size_t sz = sizeof(cpx);
-  TSD_CHECK(!ranges_overlap(x, (size_t) n * sz, y, ((size_t) (c->M - 1) * (size_t) ldy + (size_t) F) * sz),
+  const size_t sz = sizeof(cpx), szx = c->real ? sizeof(float) : sizeof(cpx);
+  const int rows = chan_rows(c);
+  TSD_CHECK(!ranges_overlap(x, (size_t) n * szx, y, ((size_t) (rows - 1) * (size_t) ldy + (size_t) F) * sz),
             "channelizer_step: x and y overlap (there is no in-place form: the layouts differ)");
   hipStream_t st = (hipStream_t) stream;
   const void *dx;
@@ -216,9 +218,10 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   int64_t dldy = F;
   bool staged = false;
   int rc;
-  if ((rc = stage_in(x, (size_t) n * sz, c->in_stage, st, &dx))) return rc;
-  if ((rc = bank_stage_out(y, ldy, c->M, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
-  if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
+  if ((rc = stage_in(x, (size_t) n * szx, c->in_stage, st, &dx))) return rc;
+  if ((rc = bank_stage_out(y, ldy, rows, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
+  if (c->real) rc = chan_real_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
+  else if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
   else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
     return chan_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
   });
@@ -226,7 +229,7 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   if (c->HW) c->cur ^= 1;
   c->phase = (int) ((c->phase + F) % c->OS);
   if (n_out) *n_out = F;
-  return bank_finish_out(y, ldy, F, c->M, sz, dy, dldy, staged, st);
+  return bank_finish_out(y, ldy, F, rows, sz, dy, dldy, staged, st);
 }
 
 int tsdgpu_channelizer_reset(tsdgpu_channelizer *c)

@@ -18,35 +18,41 @@ using cpx = float2;
 struct PolyBank {
   int M = 0, lgM = 0, K = 0, P = 0;
   int HW = 0;                           // history samples (the operator says how many, and in which order)
+  int hist_elem = sizeof(float2);       // bytes of a history sample: complex; float in the real-input channelizer
   int FP = 0;                           // pitch of a frame in the LDS image (samples)
   int cus = 0;
   float *d_tab = nullptr;               // the taps as P rows of M, then the twiddles W_M^i, i < M / 16 (one allocation)
   cpx *d_tw = nullptr;
+  cpx *d_tw2 = nullptr;                 // real-input channelizer: W_M^c, c <= M / 2, behind the twiddles (which are W_{M/2}^i there)
   void *hist[2] = {nullptr, nullptr};   // HW samples (double-buffered, one allocation)
   int cur = 0;
   bool attr_set = false;                // the kernel of this shape may take its LDS
   DevBuf in_stage, out_stage;
 };
 
-inline size_t hist_bytes(const PolyBank *c) { return (size_t) c->HW * sizeof(cpx); }
+inline size_t hist_bytes(const PolyBank *c) { return (size_t) c->HW * (size_t) c->hist_elem; }
 
 // Fills a new handle: the shape (P = `rows` tap rows of M; 0: ceil(K / M)), the device's CUs, then one allocation and one upload: the P M taps, row p
 // position s taking h[tap_index(p, s)] (zeros past K), then W_M^i, i < M / 16; and the zeroed double history of hist_len(P)
 // samples.  `who` heads the messages.  On an error the caller destroys the handle.
+// `half` = M / 2 (0: none) is the real-input channelizer's transform length: the frame pitch and the twiddles W_half^i, i < half / 16,
+// are those of a half-point transform, and the untangling table W_M^c, c <= half, follows them.
 template <typename HIST, typename INDEX>
-int polybank_init(PolyBank *c, const char *who, int M, const float *taps_host, int ntaps, HIST hist_len, INDEX tap_index, int rows = 0)
+int polybank_init(PolyBank *c, const char *who, int M, const float *taps_host, int ntaps, HIST hist_len, INDEX tap_index, int rows = 0,
+                  int half = 0)
 {
   c->M = M;
   c->lgM = __builtin_ctz((unsigned) M);
   c->K = ntaps;
   c->P = rows ? rows : (ntaps + M - 1) / M;
   c->HW = hist_len(c->P);
-  c->FP = chan_frame_pitch(M);
+  const int T = half ? half : M;        // the transform length
+  c->FP = chan_frame_pitch(T);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c->cus < 1)
     return set_err(TSDGPU_ERR_HIP, "%s: no device: %s", who, hipGetErrorString(hipGetLastError()));
-  const size_t ng = (size_t) c->P * M, ntw = (size_t) std::max(M / 16, 1);
-  std::vector<float> image(ng + 2 * ntw, 0.f);
+  const size_t ng = (size_t) c->P * M, ntw = (size_t) std::max(T / 16, 1), nun = half ? (size_t) half + 1 : 0;
+  std::vector<float> image(ng + 2 * ntw + 2 * nun, 0.f);
   for (int p = 0; p < c->P; p++)
     for (int s = 0; s < M; s++) {
       const int k = tap_index(p, s);
@@ -54,14 +60,20 @@ int polybank_init(PolyBank *c, const char *who, int M, const float *taps_host, i
     }
   const double PI = 3.14159265358979323846;
   for (size_t i = 0; i < ntw; i++) {
-    const double a = -2.0 * PI * (double) i / (double) M;
+    const double a = -2.0 * PI * (double) i / (double) T;
     image[ng + 2 * i] = (float) std::cos(a);
     image[ng + 2 * i + 1] = (float) std::sin(a);
+  }
+  for (size_t i = 0; i < nun; i++) {
+    const double a = -2.0 * PI * (double) i / (double) M;
+    image[ng + 2 * (ntw + i)] = (float) std::cos(a);
+    image[ng + 2 * (ntw + i) + 1] = (float) std::sin(a);
   }
   const size_t ib = image.size() * sizeof(float), hb = (hist_bytes(c) + 15) / 16 * 16;
   if (hipMalloc((void **) &c->d_tab, ib) != hipSuccess || (hb && hipMalloc(&c->hist[0], 2 * hb) != hipSuccess))
     return set_err(TSDGPU_ERR_ALLOC, "%s: hipMalloc of %zu bytes failed: %s", who, ib + 2 * hb, hipGetErrorString(hipGetLastError()));
   c->d_tw = reinterpret_cast<cpx *>(c->d_tab + ng);     // (ng is a multiple of 8: 8-B aligned)
+  if (half) c->d_tw2 = c->d_tw + ntw;
   if (hb) c->hist[1] = (char *) c->hist[0] + hb;
   if (hipMemcpy(c->d_tab, image.data(), ib, hipMemcpyHostToDevice) != hipSuccess || (hb && hipMemset(c->hist[0], 0, 2 * hb) != hipSuccess) ||
       hipStreamSynchronize(nullptr) != hipSuccess)
@@ -76,13 +88,14 @@ struct PolyLaunch {
   int64_t per;
   size_t lds;
 };
-inline PolyLaunch polybank_geometry(const PolyBank *c, int NPOS, int64_t F)
+inline PolyLaunch polybank_geometry(int cus, int M, int lgM, int FP, int NPOS, int64_t F)
 {
-  const int R = NPOS == 1 ? CHAN_NT >> c->lgM : 1;
+  const int R = NPOS == 1 ? CHAN_NT >> lgM : 1;
   const int64_t U = cdiv(F, 16);
-  const int grid = (int) std::min<int64_t>((int64_t) c->cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
-  return {grid, cdiv(U, (int64_t) grid * R), chan_lds_bytes(CHAN_NT * NPOS, c->M, c->FP)};
+  const int grid = (int) std::min<int64_t>((int64_t) cus * (NPOS == 1 ? 2 : 1), cdiv(U, R));
+  return {grid, cdiv(U, (int64_t) grid * R), chan_lds_bytes(CHAN_NT * NPOS, M, FP)};
 }
+inline PolyLaunch polybank_geometry(const PolyBank *c, int NPOS, int64_t F) { return polybank_geometry(c->cus, c->M, c->lgM, c->FP, NPOS, F); }
 
 // the rows of a step take 16-B loads and stores
 inline int rows_aligned(const void *rows, int64_t ld) { return ((uintptr_t) rows & 15) == 0 && (ld & 1) == 0; }

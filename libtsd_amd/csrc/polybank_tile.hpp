@@ -57,6 +57,51 @@ __device__ __forceinline__ void store_rows(const cpx *img, cpx *__restrict__ y, 
   }
 }
 
+// Row c < N of a real frame of M = 2 N samples from the N-point transform Z of its even / odd packing (channelizer_real.hip):
+// a = Z[c], b = Z[(N - c) mod N], w = W_M^c:  E = (a + conj b) / 2, O = (a - conj b) / (2 i), y_c = E + w O.
+// At c = 0 (a = b, w = 1) the imaginary part comes out as 0 exactly.
+__device__ __forceinline__ cpx untangle(cpx a, cpx b, cpx w)
+{
+  const float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);
+  const float orr = 0.5f * (a.y + b.y), oi = -0.5f * (a.x - b.x);
+  return make_float2(er + (w.x * orr - w.y * oi), ei + (w.x * oi + w.y * orr));
+}
+
+// store_rows for the real-input bank: the image holds Z = DFT_N per frame; rows c < N are untangled on the way out, a
+// (row, sub-run) pair still one 128-B segment; then row N, the Nyquist row Re Z[0] - Im Z[0], in a pass of 8 lanes per sub-run.
+__device__ __forceinline__ void store_rows_real(const cpx *img, cpx *__restrict__ y, int64_t ldy, const cpx *__restrict__ WM, int N,
+                                                int lgN, int FP, int64_t F, int64_t per, int64_t it, int R, int al, int t)
+{
+#pragma unroll 4
+  for (int u = 0; u < 8; u++) {
+    const TileItem q = tile_item(t + CHAN_NT * u, N, lgN, R, per, it);
+    const cpx *fr = img + (q.rr * 16 + 2 * q.k) * FP;
+    const int c0 = s16::pad(q.c), c1 = s16::pad((N - q.c) & (N - 1));
+    const cpx w = WM[q.c];
+    const cpx a = untangle(fr[c0], fr[c1], w), b = untangle(fr[FP + c0], fr[FP + c1], w);
+    cpx *yc = y + (int64_t) q.c * ldy + q.f;
+    if (q.f + 1 < F) {
+      if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
+      else { yc[0] = a; yc[1] = b; }
+    } else if (q.f < F) {
+      yc[0] = a;
+    }
+  }
+  if (t < 8 * R) {
+    const TileItem q = tile_item(t, 1, 0, R, per, it);     // (k, rr) = (t & 7, t >> 3)
+    const cpx *fr = img + (q.rr * 16 + 2 * q.k) * FP;
+    const cpx z0 = fr[0], z1 = fr[FP];
+    const cpx a = make_float2(z0.x - z0.y, 0.f), b = make_float2(z1.x - z1.y, 0.f);
+    cpx *yc = y + (int64_t) N * ldy + q.f;
+    if (q.f + 1 < F) {
+      if (al) *reinterpret_cast<float4 *>(yc) = make_float4(a.x, a.y, b.x, b.y);
+      else { yc[0] = a; yc[1] = b; }
+    } else if (q.f < F) {
+      yc[0] = a;
+    }
+  }
+}
+
 // The register window of a position: cur[8] its values in the 8 frames of a half unit, prev[PW] those of the PW = (PP - 1) OS
 // frames before, oldest first (OS = 1 where frames do not overlap).  Frame i of the half:
 //   sum_{p = PP-1 .. 0} g[p] frame(i - p OS), frame(k) = cur[k] (k >= 0) or prev[PW + k]: oldest sample first
@@ -71,6 +116,23 @@ __device__ __forceinline__ cpx window_chain(const float (&g)[PP], const cpx (&pr
     const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[k < 0 ? PW + k : 0];
     ar = fmaf(g[p], w.x, ar);
     ai = fmaf(g[p], w.y, ai);
+  }
+  return make_float2(ar, ai);
+}
+
+// The same chain at OS = 1 for a position that holds two real samples (.x, .y) with a tap set each: g[p].x on the .x lane,
+// g[p].y on the .y lane (the real-input bank, channelizer_real.hip).
+template <int PP>
+__device__ __forceinline__ cpx window_chain_pair(const cpx (&g)[PP], const cpx (&prev)[PP > 1 ? PP - 1 : 1], const cpx (&cur)[8], int i)
+{
+  constexpr int PW = PP - 1;
+  float ar = 0.f, ai = 0.f;
+#pragma unroll
+  for (int p = PP - 1; p >= 0; p--) {
+    const int k = i - p;
+    const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[k < 0 ? PW + k : 0];
+    ar = fmaf(g[p].x, w.x, ar);
+    ai = fmaf(g[p].y, w.y, ai);
   }
   return make_float2(ar, ai);
 }

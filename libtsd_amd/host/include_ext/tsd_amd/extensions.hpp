@@ -77,6 +77,12 @@ sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux);
 // hop; a NaN / Inf at stream position q reaches every channel of output frames floor(q / D) .. floor((q + P nb_canaux) / D) - 1,
 // P = ceil(K / nb_canaux).  Served: nb_canaux as above, K <= 16 D; else the factory fails.  surech = 1 is the factory above.
 sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux, entier surech);
+// The maximally decimated bank for a REAL stream (tsdgpu_channelizer_create_real): rows 0 .. nb_canaux / 2 of canaliseur_polyphase on
+// the widened stream; rows nb_canaux / 2 + 1 .. nb_canaux - 1 are the conjugates of rows nb_canaux / 2 - 1 .. 1 and are not
+// produced.  step(x, y): x.rows() floats, a whole number of nb_canaux-sample frames (else échec); y is resized to
+// (nb_canaux / 2 + 1) * (n / nb_canaux), channel after channel.  Host or resident vectors.  Rows 0 and nb_canaux / 2 come out with
+// an imaginary part of exactly 0.  Served: nb_canaux a power of two in [16, 1024], K <= 16 nb_canaux; else the factory fails.
+sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux);
 
 // ---- polyphase synthesizer: nb_canaux channel rows into ONE wideband complex stream (include/tsdgpu.h: tsdgpu_synthesizer) ----
 // The maximally decimated synthesis bank, the dual of canaliseur_polyphase: channel c upsampled by nb_canaux, filtered at baseband
