@@ -485,11 +485,46 @@ int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);
  *  - reconstruction: with h[k] = sin(pi (k + 1/2) / M), k < M, in the channelizer, f = h
  *    reversed here and the rows delayed by one frame, x comes back as (M OS / 2) x[p - M].
  *  - chunk invariance, layouts, alignment and the error bound are those above.
+ *
+ * Real-output bank (tsdgpu_synthesizer_create_real): M / 2 + 1 complex64 rows, what a
+ * real-input channelizer or a bank of M / 2 + 1 channels wrote, into ONE float32 stream.  With
+ * N = M / 2 and rows u_c, c = 0 .. N,
+ *     x[p] = sum_m f[p - m M] ( Re u_0[m] + (-1)^p Re u_N[m]
+ *                               + 2 sum_{0<c<N} Re( u_c[m] exp(+2 pi i c p / M) ) ):
+ * tsdgpu_synthesizer_create on the block extended by the rows M - c = conj(row c), which is
+ * exactly real.  No normalisation.  M is the transform length, as in
+ * tsdgpu_synthesizer_create: the same prototype serves both.  What changes for a real handle
+ * (tsdgpu_synthesizer_is_real() = 1):
+ *  - a step of F frames reads F samples from each of the tsdgpu_synthesizer_rows() = M / 2 + 1
+ *    rows u + c*ldu and writes n = F*M FLOATS of x; x_capacity and *n_out count floats; the
+ *    overlap check is against M / 2 + 1 rows and 4-B outputs.  x needs only 4-B alignment (an
+ *    8-B aligned x takes wider stores; the bits are the same); the rows are as above.
+ *  - the imaginary parts of rows 0 and M / 2 are NOT used (the convention of a
+ *    complex-to-real transform): any value there, a NaN included, leaves the bits of x as
+ *    they are.
+ *  - state: the last P - 1 input frames as a packed (M / 2 + 1, P - 1) complex64 block, row c
+ *    channel c's samples as the caller gave them, oldest first;
+ *    tsdgpu_synthesizer_history_len() = (P - 1) (M / 2 + 1).
+ *  - a frame has a transform of its own (of M / 2 points): its outputs do not depend on its
+ *    neighbours or on where the steps were cut, and u scaled by a power of two gives x scaled
+ *    by it, bit for bit (no overflow / underflow).
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [16, 1024], K <= 16 M, `oversample` = 1 (the argument is there for the oversampled real
+ *    bank, which is not served).  oversample < 1 is TSDGPU_ERR_INVALID.
+ *  - hop, out_count, reset, get_state / set_state, get_phase / set_phase (always 0) and destroy
+ *    serve the handle; chunk invariance, the error bound and the non-finite horizon are those
+ *    of the complex bank at OS = 1: a NaN / Inf in input frame m reaches the floats of output
+ *    frames m .. m + P - 1 and nothing else (all M of a frame when both parts of the sample are
+ *    non-finite; row M / 4 meets the exact factors i^p, so its real part alone leaves the odd
+ *    positions finite and its imaginary part alone the even ones).
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_synthesizer tsdgpu_synthesizer;
 int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps);
 int tsdgpu_synthesizer_create_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host,
                                           int ntaps);
+int tsdgpu_synthesizer_create_real(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps);
+int tsdgpu_synthesizer_rows(const tsdgpu_synthesizer *s);                           /* channels / 2 + 1 (real), channels */
+int tsdgpu_synthesizer_is_real(const tsdgpu_synthesizer *s);                        /* 1: writes a float32 stream; 0: complex64 */
 int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *s);                            /* D = channels / oversample */
 int tsdgpu_synthesizer_get_phase(const tsdgpu_synthesizer *s);                      /* hops consumed, modulo OS */
 int tsdgpu_synthesizer_set_phase(tsdgpu_synthesizer *s, int64_t hops);              /* taken modulo OS */
@@ -497,7 +532,7 @@ int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *s, int64_t frames
 int tsdgpu_synthesizer_step(tsdgpu_synthesizer *s, const void *u, int64_t ldu, int64_t frames, void *x, int64_t x_capacity,
                             int64_t *n_out, void *stream);
 int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *s);                                /* history <- zeros, phase <- 0 */
-int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * channels; OS > 1: (Q - 1) * channels */
+int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * rows; OS > 1: (Q - 1) * channels */
 int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *s, void *hist_dst, void *stream);
 int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *s, const void *hist_src, void *stream);
 int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *s);

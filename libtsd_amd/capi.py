@@ -117,6 +117,11 @@ def _declare(L):
     L.tsdgpu_channelizer_destroy.argtypes = [vp]
     L.tsdgpu_synthesizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
     L.tsdgpu_synthesizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_synthesizer_create_real.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_synthesizer_rows.argtypes = [vp]
+    L.tsdgpu_synthesizer_rows.restype = i32
+    L.tsdgpu_synthesizer_is_real.argtypes = [vp]
+    L.tsdgpu_synthesizer_is_real.restype = i32
     L.tsdgpu_synthesizer_hop.argtypes = [vp]
     L.tsdgpu_synthesizer_hop.restype = i32
     L.tsdgpu_synthesizer_get_phase.argtypes = [vp]
@@ -1119,6 +1124,78 @@ class Synthesizer:
     def set_state(self, hist=None, stream=None):
         if self.history_len:
             assert tuple(hist.shape) == (self.channels, self.frames_kept) and _dtype_code(hist) == C64
+        _check(lib().tsdgpu_synthesizer_set_state(self._h, _ptr(hist) if self.history_len else None,
+                                                  _stream_of(hist, stream) if self.history_len else stream))
+
+    def close(self):
+        if self._h:
+            lib().tsdgpu_synthesizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RealSynthesizer:
+    """Polyphase synthesis bank with a REAL output (tsdgpu_synthesizer_create_real), the dual of RealChannelizer: `rows` = M / 2 + 1
+    complex64 rows into ONE float32 stream, one launch per step.  step(u) takes the (M / 2 + 1, F) block a RealChannelizer or a
+    bank wrote and returns the F M floats
+    x[p] = sum_m f[p - m M] (Re u[0, m] + (-1)^p Re u[M / 2, m] + 2 sum_{0 < c < M / 2} Re(u[c, m] exp(+2 pi i c p / M))):
+    Synthesizer(taps, M) on the block extended by the rows M - c = conj(row c).  The imaginary parts of rows 0 and M / 2 are not
+    used.  The state is the last frames_kept = P - 1 input frames, history_len = (P - 1) (M / 2 + 1) samples."""
+
+    def __init__(self, taps, channels, oversample=1):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
+        self._h = C.c_void_p()
+        pt = t.ctypes.data if len(t) else None
+        _check(lib().tsdgpu_synthesizer_create_real(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
+        self.rows = lib().tsdgpu_synthesizer_rows(self._h)
+        self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
+        self.frames_kept = self.history_len // self.rows                # P - 1
+        self.hop = lib().tsdgpu_synthesizer_hop(self._h)
+
+    def out_count(self, frames):
+        return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
+
+    def step(self, u, x=None, stream=None):
+        """u: (rows, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
+        x: 1-D float32 with at least F M samples, of u's kind (default: a new one); returns its first F M samples."""
+        if _dtype_code(u) != C64 or u.ndim != 2:
+            raise TsdGpuError("the real-output synthesizer takes a 2-D (channels / 2 + 1, frames) complex64 block")
+        pu, ldu = _ptr2d(u, self.rows)
+        F = int(u.shape[1])
+        if x is None:
+            if isinstance(u, np.ndarray):
+                x = np.empty(F * self.hop, np.float32)
+            else:
+                import torch
+                x = u.new_empty(F * self.hop, dtype=torch.float32)
+        if _dtype_code(x) != F32 or x.ndim != 1:
+            raise TsdGpuError("the real-output synthesizer writes a 1-D float32 stream")
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_synthesizer_step(self._h, pu, ldu, F, _ptr(x), int(x.shape[0]), C.byref(got), _stream_of(u, stream)))
+        return x[: got.value]
+
+    def reset(self):
+        _check(lib().tsdgpu_synthesizer_reset(self._h))
+
+    def get_state(self, dst=None, stream=None):
+        """the last P - 1 input frames as an (M / 2 + 1, P - 1) block: row c = channel c's last inputs, oldest first.
+        dst: packed complex64 numpy array or torch tensor."""
+        shape = (self.rows, self.frames_kept)
+        if dst is None:
+            dst = np.zeros(shape, np.complex64)
+        assert tuple(dst.shape) == shape and _dtype_code(dst) == C64
+        _check(lib().tsdgpu_synthesizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
+        return dst
+
+    def set_state(self, hist=None, stream=None):
+        if self.history_len:
+            assert tuple(hist.shape) == (self.rows, self.frames_kept) and _dtype_code(hist) == C64
         _check(lib().tsdgpu_synthesizer_set_state(self._h, _ptr(hist) if self.history_len else None,
                                                   _stream_of(hist, stream) if self.history_len else stream))
 

@@ -2,7 +2,8 @@
 // synthesizer_os.hip): a
 // workgroup of CHAN_NT threads, R = CHAN_NT / M sub-runs of 16-frame units, one LDS image of 16 R frames at pitch FP
 // (channelizer_internal.hpp).  Here are the thread's place in that tile, the channel-major read-back of the two analysis banks,
-// and the register window of a position with its fma chains.  Where a bank's samples come from and where its frames go stays in
+// the real banks' untangling (channelizer_real.hip) and tangling (synthesizer_real.hip) steps, and the register window of a
+// position with its fma chains.  Where a bank's samples come from and where its frames go stays in
 // its own file, and so does the in-LDS transform of the tile (the R0 == 0 / s16::transform block): the files are built with
 // -ffp-contract=fast, and behind a function the twiddle products of that block fuse differently and give other bits.
 #pragma once
@@ -100,6 +101,31 @@ __device__ __forceinline__ void store_rows_real(const cpx *img, cpx *__restrict_
       yc[0] = a;
     }
   }
+}
+
+// untangle backwards, for the real-output synthesizer (synthesizer_real.hip): from the rows a = U_c, b = U_{N-c}, 0 < c < N / 2,
+// and w = W_M^c the two inputs of the N-point inverse transform,
+//   Z_c = A + T,  Z_{N-c} = conj A - conj T,   A = a + conj b,  T = i conj(w) (a - conj b)
+// (W_M^{N-c} = -conj w), written to zc, zn with re and im swapped: the forward transform then serves as the inverse.
+__device__ __forceinline__ void tangle_store(cpx *zc, cpx *zn, cpx a, cpx b, cpx w)
+{
+  const float ar = a.x + b.x, ai = a.y - b.y;
+  const float dr = a.x - b.x, di = a.y + b.y;
+  const float tr = w.y * dr - w.x * di, ti = w.x * dr + w.y * di;
+  *zc = make_float2(ai + ti, ar + tr);
+  *zn = make_float2(ti - ai, ar - tr);
+}
+
+// the lone pairs of that pass, swapped alike.  Z_0 = (Re U_0 + Re U_N) + i (Re U_0 - Re U_N): the imaginary parts of the rows 0
+// and N are not used.  Z_{N/2} = 2 conj U_{N/2} (W_M^{N/2} = -i).
+__device__ __forceinline__ cpx tangle_edge(cpx u0, cpx un) { return make_float2(u0.x - un.x, u0.x + un.x); }
+__device__ __forceinline__ cpx tangle_mid(cpx um) { return make_float2(-2.f * um.y, 2.f * um.x); }
+
+// two neighbouring real samples of a float stream: one 8-B store where the stream is 8-B aligned (xal), two 4-B stores where not
+__device__ __forceinline__ void store_pair(float *__restrict__ p, cpx v, int xal)
+{
+  if (xal) *reinterpret_cast<cpx *>(p) = v;
+  else { p[0] = v.x; p[1] = v.y; }
 }
 
 // The register window of a position: cur[8] its values in the 8 frames of a half unit, prev[PW] those of the PW = (PP - 1) OS

@@ -20,7 +20,7 @@
 // the handle's history when they lie before the step.  The last workgroup writes the new history (the last P - 1 input frames of
 // old history ++ u, per channel) into the other buffer.
 // The oversampled bank (hop D = M / OS, OS in {2, 4}) is the sibling kernel of synthesizer_os.hip; the handle and the entry points
-// below serve both.
+// below serve both.  And the real-output bank (synthesizer_real.hip: M / 2 + 1 rows into a float32 stream): x counts floats there.
 #include "common.hpp"
 #include "bank_internal.hpp"
 #include "synthesizer_handle.hpp"
@@ -231,8 +231,9 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   TSD_CHECK(u != nullptr && x != nullptr, "synthesizer_step: NULL buffer");
   TSD_CHECK(n <= x_capacity, "synthesizer_step: the output needs %lld samples, x_capacity is %lld", (long long) n, (long long) x_capacity);
   TSD_CHECK(ldu >= F, "synthesizer_step: ldu = %lld below the %lld inputs of a channel", (long long) ldu, (long long) F);
-  const size_t sz = sizeof(cpx);
-  TSD_CHECK(!ranges_overlap(x, (size_t) n * sz, u, ((size_t) (c->M - 1) * (size_t) ldu + (size_t) F) * sz),
+  const size_t sz = sizeof(cpx), szx = c->real ? sizeof(float) : sizeof(cpx);
+  const int rows = syn_rows(c);
+  TSD_CHECK(!ranges_overlap(x, (size_t) n * szx, u, ((size_t) (rows - 1) * (size_t) ldu + (size_t) F) * sz),
             "synthesizer_step: u and x overlap (there is no in-place form: the layouts differ)");
   hipStream_t st = (hipStream_t) stream;
   const void *du;
@@ -240,9 +241,10 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   int64_t dldu = F;
   bool staged = false;
   int rc;
-  if ((rc = bank_stage_in(u, ldu, F, c->M, sz, false, F, c->in_stage, st, &du, &dldu))) return rc;
-  if ((rc = stage_out(x, (size_t) n * sz, c->out_stage, &dx, &staged))) return rc;
-  if (c->OS > 1) rc = syn_os_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
+  if ((rc = bank_stage_in(u, ldu, F, rows, sz, false, F, c->in_stage, st, &du, &dldu))) return rc;
+  if ((rc = stage_out(x, (size_t) n * szx, c->out_stage, &dx, &staged))) return rc;
+  if (c->real) rc = syn_real_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
+  else if (c->OS > 1) rc = syn_os_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
   else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
     return syn_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
   });
@@ -250,7 +252,7 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   if (c->HW) c->cur ^= 1;
   c->phase = (int) ((c->phase + F) % c->OS);
   if (n_out) *n_out = n;
-  return finish_out(x, (size_t) n * sz, dx, staged, st);
+  return finish_out(x, (size_t) n * szx, dx, staged, st);
 }
 
 int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *c)

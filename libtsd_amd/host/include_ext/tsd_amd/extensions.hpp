@@ -98,6 +98,12 @@ sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux);
 // reaches every sample of output hops m .. m + ceil(K / D) - 1.  Served: nb_canaux as above, K <= 16 D; else the factory fails.
 // surech = 1 is the factory above.
 sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux, entier surech);
+// The maximally decimated bank with a REAL output (tsdgpu_synthesizer_create_real), the way back from canaliseur_polyphase_reel:
+// synthetiseur_polyphase on the block extended by the rows nb_canaux - c = conj(row c), whose output is real.  step(x, y):
+// x.rows() = (nb_canaux / 2 + 1) blocks of F samples, channel after channel (else échec); y is resized to nb_canaux * F floats.
+// Host or resident vectors.  The imaginary parts of rows 0 and nb_canaux / 2 are not used: any value there, a NaN included, leaves
+// the output as it is.  Served: nb_canaux a power of two in [16, 1024], K <= 16 nb_canaux; else the factory fails.
+sptr<FiltreGen<cfloat, float>> synthetiseur_polyphase_reel(const Vecf &h, entier nb_canaux);
 
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
