@@ -407,17 +407,41 @@ int tsdgpu_polyfir_bank_destroy(tsdgpu_polyfir_bank *b);
  *    neighbours or on where the steps were cut, and x scaled by a power of two gives y scaled
  *    by it, bit for bit (no overflow / underflow).
  *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
- *    [16, 1024], K <= 16 M, `oversample` = 1 (the argument is there for the oversampled real
- *    bank, which is not served).  oversample < 1 is TSDGPU_ERR_INVALID.
+ *    [16, 1024], K <= 16 M, `oversample` = 1 (the oversampled real bank has an entry of its
+ *    own, below).  oversample < 1 is TSDGPU_ERR_INVALID.
  *  - hop, out_count, reset, get_state / set_state, get_phase / set_phase (always 0) and destroy
  *    serve the handle; chunk invariance, the error bound and the non-finite horizon are those
  *    of the complex bank at OS = 1.
+ *
+ * Oversampled real-input bank (tsdgpu_channelizer_create_real_oversampled): the real-input bank
+ * with a new frame every D = M / OS floats, OS = `oversample` in {1, 2, 4}: rows 0 .. M / 2 of
+ * the oversampled bank on the stream widened to complex64.  OS = 1 is
+ * tsdgpu_channelizer_create_real, its handle, kernel and bits.  What changes for a real handle
+ * with OS > 1:
+ *  - a step takes n = F*D FLOATS (F whole hops) and writes F complex64 outputs to each of the
+ *    M / 2 + 1 rows; n % D != 0 is TSDGPU_ERR_INVALID and advances nothing; out_count, hop,
+ *    y_capacity, ldy and the overlap check are against F = n / D, 4-B inputs and M / 2 + 1 rows.
+ *  - state, two parts, as for the oversampled complex bank.  History: the last
+ *    tsdgpu_channelizer_history_len() = P M - D input FLOATS, oldest first.  Phase: the hops
+ *    consumed modulo OS, moved by get_phase / set_phase.  Both moved to a fresh handle continue
+ *    the stream bit for bit; the history alone does not.
+ *  - rows 0 and M / 2 have an imaginary part of exactly 0; a frame has a transform of its own,
+ *    so the bits do not depend on where the steps were cut and x scaled by a power of two gives
+ *    y scaled by it, bit for bit; x needs only 4-B alignment and rows only 8-B alignment, the
+ *    wider paths giving the same bits.
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [16, 1024], OS in {1, 2, 4}, K <= 16 D.  OS < 1, M < 1, K < 1 and NULL pointers are
+ *    TSDGPU_ERR_INVALID.  Rational oversampling is not served.
+ *  - non-finite inputs: a NaN / Inf at stream position q makes ALL rows of output frames
+ *    floor(q / D) .. floor((q + P M) / D) - 1 non-finite and nothing else.
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_channelizer tsdgpu_channelizer;
 int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps);
 int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host,
                                           int ntaps);
 int tsdgpu_channelizer_create_real(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps);
+int tsdgpu_channelizer_create_real_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host,
+                                               int ntaps);
 int tsdgpu_channelizer_rows(const tsdgpu_channelizer *c);                       /* channels / 2 + 1 (real), channels */
 int tsdgpu_channelizer_is_real(const tsdgpu_channelizer *c);                    /* 1: a float32 stream; 0: complex64 */
 int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c);                        /* D = channels / oversample */

@@ -97,6 +97,7 @@ def _declare(L):
     L.tsdgpu_channelizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
     L.tsdgpu_channelizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
     L.tsdgpu_channelizer_create_real.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_channelizer_create_real_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
     L.tsdgpu_channelizer_rows.argtypes = [vp]
     L.tsdgpu_channelizer_rows.restype = i32
     L.tsdgpu_channelizer_is_real.argtypes = [vp]
@@ -996,25 +997,45 @@ class RealChannelizer:
     complex64 rows, one launch per step.  step(x) takes n = F M floats and returns the (M / 2 + 1, F) block
     y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m M + M - 1, c <= M / 2: the rows of Channelizer(taps, M) on
     the widened stream that are not the conjugates of others (row M - c = conj row c), in the (C, n) layout the banks read.
-    The state is the last history_len = (P - 1) M floats."""
+    The state is the last history_len = (P - 1) M floats.
+    RealChannelizer.oversampled(taps, M, OS), OS in {1, 2, 4} (tsdgpu_channelizer_create_real_oversampled): a new frame every
+    hop D = M / OS floats, n_m = m D + D - 1: rows 0 .. M / 2 of Channelizer(taps, M, oversample=OS) on the widened stream.
+    step(x) takes n = F D floats.  For OS > 1 the state is the last history_len = P M - D floats and `phase`, the hops consumed
+    so far modulo OS: move both to continue a stream in a fresh handle.  The constructor itself serves oversample = 1 only."""
 
-    def __init__(self, taps, channels, oversample=1):
+    def __init__(self, taps, channels, oversample=1, _create=None):
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
         self._h = C.c_void_p()
         pt = t.ctypes.data if len(t) else None
-        _check(lib().tsdgpu_channelizer_create_real(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
+        create = _create if _create is not None else lib().tsdgpu_channelizer_create_real
+        _check(create(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
         self.rows = lib().tsdgpu_channelizer_rows(self._h)
         self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
         self.hop = lib().tsdgpu_channelizer_hop(self._h)
+
+    @classmethod
+    def oversampled(cls, taps, channels, oversample):
+        """the bank at hop D = channels / oversample, oversample in {1, 2, 4} (1: the bank and the bits of the constructor)"""
+        return cls(taps, channels, oversample, _create=lib().tsdgpu_channelizer_create_real_oversampled)
+
+    @property
+    def phase(self):
+        """hops consumed so far, modulo `oversample` (always 0 at oversample = 1)"""
+        return lib().tsdgpu_channelizer_get_phase(self._h)
+
+    @phase.setter
+    def phase(self, hops):
+        _check(lib().tsdgpu_channelizer_set_phase(self._h, int(hops)))
 
     def out_count(self, n):
         return lib().tsdgpu_channelizer_out_count(self._h, int(n))
 
     def step(self, x, y=None, stream=None):
-        """x: 1-D float32 numpy array (host) or torch tensor (host or device), a whole number of frames of M samples.
-        y: (rows, m) complex64 with m >= n / M, of x's kind, rows may be strided (default: a new packed one); returns its
-        (rows, n / M) view."""
+        """x: 1-D float32 numpy array (host) or torch tensor (host or device), a whole number of hops of D = M / oversample
+        floats (frames of M at oversample = 1).
+        y: (rows, m) complex64 with m >= n / D, of x's kind, rows may be strided (default: a new packed one); returns its
+        (rows, n / D) view."""
         if _dtype_code(x) != F32 or x.ndim != 1:
             raise TsdGpuError("the real-input channelizer takes a 1-D float32 stream")
         n = int(x.shape[0])
@@ -1036,7 +1057,8 @@ class RealChannelizer:
         _check(lib().tsdgpu_channelizer_reset(self._h))
 
     def get_state(self, dst=None, stream=None):
-        """the last history_len = (P - 1) M input floats, oldest first.  dst: packed float32 numpy array or torch tensor."""
+        """the last history_len = P M - D input floats ((P - 1) M at oversample = 1), oldest first.  dst: packed float32 numpy
+        array or torch tensor.  For oversample > 1 the state has a second part, `phase`."""
         if dst is None:
             dst = np.zeros(self.history_len, np.float32)
         assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == F32

@@ -18,7 +18,7 @@
 // The last workgroup writes the new history (the last (P - 1) M samples of old history ++ x) into the other buffer.
 // The handle also serves the oversampled bank (hop D = M / OS, OS in {2, 4}): its kernel family is channelizer_os.hip, and the
 // entry points below count a step in hops of D samples; at OS = 1 they are what they were.  And the real-input bank
-// (channelizer_real.hip: a float32 stream into M / 2 + 1 rows): n and the history count floats there.
+// (channelizer_real.hip: a float32 stream into M / 2 + 1 rows; channelizer_real_os.hip at OS > 1): n and the history count floats there.
 // Shared with channelizer_os.hip and synthesizer.hip: polybank_tile.hpp (device; it says why the transform block is not in it) and
 // polybank_host.hpp (the handle: what it holds, how it is filled, launched and moved).
 #include "common.hpp"
@@ -220,7 +220,8 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   int rc;
   if ((rc = stage_in(x, (size_t) n * szx, c->in_stage, st, &dx))) return rc;
   if ((rc = bank_stage_out(y, ldy, rows, sz, false, F, c->out_stage, &dy, &dldy, &staged))) return rc;
-  if (c->real) rc = chan_real_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
+  if (c->real && c->OS > 1) rc = chan_real_os_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
+  else if (c->real) rc = chan_real_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
   else if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
   else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
     return chan_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);

@@ -163,7 +163,8 @@ int tsdgpu_channelizer_create_real(tsdgpu_channelizer **out, int channels, int o
     return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: channels = %d: served are the powers of two from %d to %d", channels,
                    CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
   if (oversample != 1)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: oversample = %d: the real-input bank serves 1 only", oversample);
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: oversample = %d: served is 1 (tsdgpu_channelizer_create_real_oversampled serves 2 and 4)",
+                   oversample);
   if (ntaps > CHAN_MAX_P * channels)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
                    ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);

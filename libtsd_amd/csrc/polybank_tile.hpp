@@ -163,6 +163,24 @@ __device__ __forceinline__ cpx window_chain_pair(const cpx (&g)[PP], const cpx (
   return make_float2(ar, ai);
 }
 
+// The pair chain where frames overlap (the oversampled real-input bank, channelizer_real_os.hip): the position's pairs lie D
+// apart and the chain takes every OS-th, as window_chain<PP, OS> does, with the two tap sets of window_chain_pair.
+template <int PP, int OS>
+__device__ __forceinline__ cpx window_chain_pair_os(const cpx (&g)[PP], const cpx (&prev)[PP > 1 ? (PP - 1) * OS : 1], const cpx (&cur)[8],
+                                                    int i)
+{
+  constexpr int PW = (PP - 1) * OS;
+  float ar = 0.f, ai = 0.f;
+#pragma unroll
+  for (int p = PP - 1; p >= 0; p--) {
+    const int k = i - p * OS;
+    const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[k < 0 ? PW + k : 0];
+    ar = fmaf(g[p].x, w.x, ar);
+    ai = fmaf(g[p].y, w.y, ai);
+  }
+  return make_float2(ar, ai);
+}
+
 // the window moves on by the half unit: prev = the last PW of (prev ++ cur)
 template <int PW> __device__ __forceinline__ void window_shift(cpx (&prev)[PW > 0 ? PW : 1], const cpx (&cur)[8])
 {

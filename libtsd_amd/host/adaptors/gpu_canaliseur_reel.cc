@@ -4,6 +4,8 @@
 // conjugates and are not produced.
 // step(x, y): x.rows() = n floats must be a whole number of nb_canaux-sample frames; y is resized to nb_canaux / 2 + 1 blocks of
 // n / nb_canaux samples, channel after channel -- the layout filtre_rif_canaux::step and the other banks take; host or resident vectors.
+// With surech = OS in {2, 4} (the three-argument factory; tsdgpu_channelizer_create_real_oversampled) the bank is oversampled: a
+// frame every D = nb_canaux / OS floats, n a whole number of hops of D floats, y nb_canaux / 2 + 1 blocks of n / D samples.
 #include "gpu_commun.hpp"
 #include "tsd_amd/extensions.hpp"
 
@@ -11,20 +13,25 @@ namespace tsd_amd {
 
 struct CanaliseurReelGpu : FiltreGen<float, cfloat> {
   tsdgpu_channelizer *h = nullptr;
-  entier M, C;                          // frame length, rows
-  CanaliseurReelGpu(const Vecf &taps, entier nb_canaux) : M(nb_canaux), C(nb_canaux / 2 + 1)
+  entier M, C, D;                       // frame length, rows, hop
+  CanaliseurReelGpu(const Vecf &taps, entier nb_canaux, entier surech) : M(nb_canaux), C(nb_canaux / 2 + 1), D(nb_canaux)
   {
     if (nb_canaux < 1) échec("canaliseur_polyphase_reel: nb_canaux >= 1 required ({})", (int) nb_canaux);
+    if (surech < 1) échec("canaliseur_polyphase_reel: surech >= 1 required ({})", (int) surech);
     if (taps.rows() <= 0) échec("canaliseur_polyphase_reel: K > 0 required (K = {})", (int) taps.rows());
-    if (tsdgpu_channelizer_create_real(&h, (int) nb_canaux, 1, taps.data(), (int) taps.rows())) gpu_fail("canaliseur_polyphase_reel");
+    const int rc = surech == 1 ? tsdgpu_channelizer_create_real(&h, (int) nb_canaux, 1, taps.data(), (int) taps.rows())
+                               : tsdgpu_channelizer_create_real_oversampled(&h, (int) nb_canaux, (int) surech, taps.data(), (int) taps.rows());
+    if (rc) gpu_fail("canaliseur_polyphase_reel");
     C = tsdgpu_channelizer_rows(h);
+    D = tsdgpu_channelizer_hop(h);
   }
   ~CanaliseurReelGpu() { tsdgpu_channelizer_destroy(h); }
   void step(const Vecteur<float> &x, Vecteur<cfloat> &y)
   {
     const entier n = x.rows();
-    if (n % M != 0) échec("canaliseur_polyphase_reel::step: {} samples are not a whole number of {}-sample frames", (int) n, (int) M);
-    const int64_t F = n / M;
+    if (n % D != 0)
+      échec("canaliseur_polyphase_reel::step: {} samples are not a whole number of {}-sample {}", (int) n, (int) D, D == M ? "frames" : "hops");
+    const int64_t F = n / D;
     if ((const void *) x.data() == (const void *) y.data() && n > 0) échec("canaliseur_polyphase_reel::step: x and y share their memory");
     sortie_variable(x, y, (long long) C * F, [&](cfloat *out) {
       int64_t got = 0;
@@ -33,6 +40,14 @@ struct CanaliseurReelGpu : FiltreGen<float, cfloat> {
   }
 };
 
-sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux) { return std::make_shared<CanaliseurReelGpu>(h, nb_canaux); }
+sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux)
+{
+  return std::make_shared<CanaliseurReelGpu>(h, nb_canaux, 1);
+}
+
+sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux, entier surech)
+{
+  return std::make_shared<CanaliseurReelGpu>(h, nb_canaux, surech);
+}
 
 }  // namespace tsd_amd

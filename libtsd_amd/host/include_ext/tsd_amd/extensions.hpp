@@ -83,6 +83,12 @@ sptr<FiltreGen<cfloat>> canaliseur_polyphase(const Vecf &h, entier nb_canaux, en
 // (nb_canaux / 2 + 1) * (n / nb_canaux), channel after channel.  Host or resident vectors.  Rows 0 and nb_canaux / 2 come out with
 // an imaginary part of exactly 0.  Served: nb_canaux a power of two in [16, 1024], K <= 16 nb_canaux; else the factory fails.
 sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux);
+// The same bank oversampled by surech = OS in {1, 2, 4} (tsdgpu_channelizer_create_real_oversampled): a frame every
+// D = nb_canaux / OS floats, rows 0 .. nb_canaux / 2 of canaliseur_polyphase(h, nb_canaux, surech) on the widened stream.
+// step(x, y): x.rows() floats, a whole number of hops of D (else échec); y is resized to (nb_canaux / 2 + 1) * (n / D), channel
+// after channel.  The object carries the history and the phase of the hop.  Served: nb_canaux as above, K <= 16 D; else the
+// factory fails (surech < 1 included).  surech = 1 is the factory above and its bits.
+sptr<FiltreGen<float, cfloat>> canaliseur_polyphase_reel(const Vecf &h, entier nb_canaux, entier surech);
 
 // ---- polyphase synthesizer: nb_canaux channel rows into ONE wideband complex stream (include/tsdgpu.h: tsdgpu_synthesizer) ----
 // The maximally decimated synthesis bank, the dual of canaliseur_polyphase: channel c upsampled by nb_canaux, filtered at baseband
