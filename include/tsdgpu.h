@@ -14,7 +14,32 @@
  *    D2H) and the call returns after the result is in the host buffer.  Coefficient
  *    pointers given to *_create are always HOST pointers and are copied.
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls with
- *    device pointers are asynchronous on that stream.
+ *    device pointers are asynchronous on that stream: every launch, copy and memset of the
+ *    call -- private copies for in-place and misaligned buffers and the update of the handle's
+ *    device state included -- goes to that stream and to no other (never to the null stream,
+ *    which non-blocking streams are not ordered with), x is not read once the call's work on the
+ *    stream has run, and the call returns without waiting for the stream.  The host side of a
+ *    handle's state (which of its two history buffers is current, phase and block counters, a
+ *    resampler's position) advances at enqueue time: enqueue the steps of one handle in stream
+ *    order -- on one stream, or on several with events between them (an FFT / real-FFT plan
+ *    orders steps from different streams itself).
+ *    The calls that wait on the host although their pointers are device pointers, each with its
+ *    reason, are the host-synchronous rows of the table in DESIGN.md, "The stream contract":
+ *    what returns values to the host (tsdgpu_vec_reduce, tsdgpu_welch, tsdgpu_delay_estimate,
+ *    tsdgpu_detector_step, tsdgpu_ola_read_spectra, tsdgpu_sos_get_state,
+ *    tsdgpu_sos_bank_get_state), what takes a state or spectra from a host vector that may die
+ *    with the caller's scope (tsdgpu_sos_set_state, tsdgpu_sos_bank_set_state,
+ *    tsdgpu_ola_write_spectra), tsdgpu_xcorr (its plan and scratch go back to a reserve for the
+ *    next caller) and tsdgpu_synchronize.  An asynchronous call may still wait when it
+ *    must grow a scratch buffer of its handle (first use, a larger n than any before); so may
+ *    the first tsdgpu_sos_step of a new exact-carry chunk length and a tsdgpu_resampler_step
+ *    that reaches stream positions the handle has not reached before (both upload tables from
+ *    host vectors).  Run one step of the largest size first where that matters.
+ *  - *_reset without a stream argument is a memset on the null stream plus a wait for the null
+ *    stream: steps enqueued AFTER it, on any stream, see the zeros, but it is not ordered with
+ *    steps still in flight on a non-blocking stream.  Synchronise those streams first, or use
+ *    tsdgpu_fir_reset_on / tsdgpu_sos_reset_on / tsdgpu_spectrum_reset, which are ordered on the
+ *    caller's stream and do not wait.
  *  - handles are stateful exactly like the reference's filter objects (streaming: state
  *    is carried from one step to the next) and, like them, not thread-safe.
  *  - complex samples are interleaved (re, im) float32 pairs == std::complex<float>.

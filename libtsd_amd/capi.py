@@ -531,8 +531,10 @@ class Spectrum:
         assert got.value == nout
         return y
 
-    def reset(self):
-        _check(lib().tsdgpu_spectrum_reset(self._h, None))
+    def reset(self, stream=None):
+        """sums and block count <- zero, ordered on `stream` (no host wait; None: the null stream, which non-blocking streams
+        are not ordered with -- synchronise before stepping on one of those, or pass the stream the steps use)"""
+        _check(lib().tsdgpu_spectrum_reset(self._h, stream))
 
     def close(self):
         if self._h:

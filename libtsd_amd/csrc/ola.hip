@@ -1189,7 +1189,7 @@ int tsdgpu_ola_step(tsdgpu_ola *h, const void *x, int64_t n, void *y, int64_t *n
     if ((rc = ola1024_launch(dx, (cpx *) dyv, h->d_fast, h->d_svg, h->d_svg_tmp, B, st))) return rc;
     std::swap(h->d_svg, h->d_svg_tmp);            // (the last wave wrote the new tail beside the one the first wave read)
     if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged) TSD_HIP(hipStreamSynchronize(st));    // (a staged input must outlive its kernels)
+    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
     h->nrest = (int) left;
     h->cnt_ech += nout;
     if (n_out) *n_out = nout;
@@ -1225,7 +1225,7 @@ int tsdgpu_ola_step(tsdgpu_ola *h, const void *x, int64_t n, void *y, int64_t *n
       TSD_HIP(hipGetLastError());
     }
     if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged) TSD_HIP(hipStreamSynchronize(st));    // (a staged input must outlive its kernels)
+    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
     h->nrest = (int) left;
     h->cnt_ech += nout;
     if (n_out) *n_out = nout;
@@ -1272,7 +1272,7 @@ int tsdgpu_ola_step(tsdgpu_ola *h, const void *x, int64_t n, void *y, int64_t *n
       TSD_HIP(hipGetLastError());
     }
     if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged) TSD_HIP(hipStreamSynchronize(st));    // (a staged input must outlive its kernels)
+    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
     h->nrest = (int) left;
     h->cnt_ech += B * Ne;
     if (n_out) *n_out = nout;
