@@ -558,20 +558,51 @@ int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c);
  *    neighbours or on where the steps were cut, and u scaled by a power of two gives x scaled
  *    by it, bit for bit (no overflow / underflow).
  *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
- *    [16, 1024], K <= 16 M, `oversample` = 1 (the argument is there for the oversampled real
- *    bank, which is not served).  oversample < 1 is TSDGPU_ERR_INVALID.
+ *    [16, 1024], K <= 16 M, `oversample` = 1 (this entry refuses every other value; the
+ *    oversampled real bank has the entry below).  oversample < 1 is TSDGPU_ERR_INVALID.
  *  - hop, out_count, reset, get_state / set_state, get_phase / set_phase (always 0) and destroy
  *    serve the handle; chunk invariance, the error bound and the non-finite horizon are those
  *    of the complex bank at OS = 1: a NaN / Inf in input frame m reaches the floats of output
  *    frames m .. m + P - 1 and nothing else (all M of a frame when both parts of the sample are
  *    non-finite; row M / 4 meets the exact factors i^p, so its real part alone leaves the odd
  *    positions finite and its imaginary part alone the even ones).
+ *
+ * Oversampled real-output bank (tsdgpu_synthesizer_create_real_oversampled): the M / 2 + 1
+ * rows of an oversampled real-input channelizer (tsdgpu_channelizer_create_real_oversampled)
+ * or of the banks behind it, one frame per hop of D = M / OS FLOATS, OS = `oversample` in
+ * {1, 2, 4}, back into one float32 stream.  With p counted over the whole stream,
+ *     x[p] = sum_m f[p - m D] ( Re u_0[m] + (-1)^p Re u_N[m]
+ *                               + 2 sum_{0<c<N} Re( u_c[m] exp(+2 pi i c p / M) ) ):
+ * tsdgpu_synthesizer_create_oversampled on the block extended by the rows M - c = conj(row c),
+ * exactly real; no normalisation; no conjugate rows are built and no imaginary part is
+ * written.  OS = 1 is tsdgpu_synthesizer_create_real, its handle, kernel and bits.  For OS > 1
+ * the handle is a real handle (is_real = 1, rows = M / 2 + 1) and an oversampled one:
+ *  - a step of F frames reads F samples from each of the M / 2 + 1 rows and writes n = F*D
+ *    floats (hop = D); x_capacity, *n_out and the overlap check count floats.  x needs 4-B
+ *    alignment only, as above.
+ *  - state, two parts.  History: the last Q - 1 input frames, Q = ceil(K / D), as the packed
+ *    (M / 2 + 1, Q - 1) complex64 block, the samples as the caller gave them;
+ *    tsdgpu_synthesizer_history_len() = (Q - 1) (M / 2 + 1).  Phase: the hops consumed so far
+ *    modulo OS, with the rules of the oversampled complex bank: move both to a fresh handle.
+ *  - limits (create returns TSDGPU_ERR_UNSUPPORTED, never a step): M a power of two in
+ *    [16, 1024], OS in {1, 2, 4}, K <= 16 D.  A NULL `out`, channels < 1, oversample < 1 or no
+ *    taps are TSDGPU_ERR_INVALID.
+ *  - the imaginary parts of rows 0 and M / 2 are not used; a frame has a transform of its own;
+ *    chunk invariance, exact scaling by powers of two, layouts and the error bound are those
+ *    of the real bank; a NaN / Inf in input frame m reaches the floats of output hops
+ *    m .. m + Q - 1 and nothing else (row M / 4 as above: one part alone leaves every other
+ *    float of those hops finite).
+ *  - reconstruction: with h[k] = sin(pi (k + 1/2) / M), k < M, in the real-input channelizer at
+ *    the same OS, f = h reversed here and the rows delayed by one frame, x comes back as
+ *    (M OS / 2) x[p - M].
  * ------------------------------------------------------------------------------------ */
 typedef struct tsdgpu_synthesizer tsdgpu_synthesizer;
 int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps);
 int tsdgpu_synthesizer_create_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host,
                                           int ntaps);
 int tsdgpu_synthesizer_create_real(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps);
+int tsdgpu_synthesizer_create_real_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host,
+                                               int ntaps);
 int tsdgpu_synthesizer_rows(const tsdgpu_synthesizer *s);                           /* channels / 2 + 1 (real), channels */
 int tsdgpu_synthesizer_is_real(const tsdgpu_synthesizer *s);                        /* 1: writes a float32 stream; 0: complex64 */
 int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *s);                            /* D = channels / oversample */
@@ -581,7 +612,7 @@ int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *s, int64_t frames
 int tsdgpu_synthesizer_step(tsdgpu_synthesizer *s, const void *u, int64_t ldu, int64_t frames, void *x, int64_t x_capacity,
                             int64_t *n_out, void *stream);
 int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *s);                                /* history <- zeros, phase <- 0 */
-int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * rows; OS > 1: (Q - 1) * channels */
+int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *s);                    /* (P - 1) * rows; OS > 1: (Q - 1) * rows */
 int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *s, void *hist_dst, void *stream);
 int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *s, const void *hist_src, void *stream);
 int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *s);

@@ -119,6 +119,7 @@ def _declare(L):
     L.tsdgpu_synthesizer_create.argtypes = [C.POINTER(vp), i32, vp, i32]
     L.tsdgpu_synthesizer_create_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
     L.tsdgpu_synthesizer_create_real.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
+    L.tsdgpu_synthesizer_create_real_oversampled.argtypes = [C.POINTER(vp), i32, i32, vp, i32]
     L.tsdgpu_synthesizer_rows.argtypes = [vp]
     L.tsdgpu_synthesizer_rows.restype = i32
     L.tsdgpu_synthesizer_is_real.argtypes = [vp]
@@ -1169,25 +1170,46 @@ class RealSynthesizer:
     bank wrote and returns the F M floats
     x[p] = sum_m f[p - m M] (Re u[0, m] + (-1)^p Re u[M / 2, m] + 2 sum_{0 < c < M / 2} Re(u[c, m] exp(+2 pi i c p / M))):
     Synthesizer(taps, M) on the block extended by the rows M - c = conj(row c).  The imaginary parts of rows 0 and M / 2 are not
-    used.  The state is the last frames_kept = P - 1 input frames, history_len = (P - 1) (M / 2 + 1) samples."""
+    used.  The state is the last frames_kept = P - 1 input frames, history_len = (P - 1) (M / 2 + 1) samples.
+    RealSynthesizer.oversampled(taps, M, OS), OS in {1, 2, 4} (tsdgpu_synthesizer_create_real_oversampled): a frame per hop of
+    D = M / OS floats, f[p - m D] in the sum and p counted over the whole stream: Synthesizer(taps, M, oversample=OS) on the
+    extended block, the way back from RealChannelizer.oversampled.  step(u) returns F D floats.  For OS > 1 the state is the last
+    frames_kept = Q - 1 input frames, Q = ceil(K / D), and `phase`, the hops consumed so far modulo OS: move both to continue a
+    stream in a fresh handle.  The constructor itself serves oversample = 1 only."""
 
-    def __init__(self, taps, channels, oversample=1):
+    def __init__(self, taps, channels, oversample=1, _create=None):
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
         self._h = C.c_void_p()
         pt = t.ctypes.data if len(t) else None
-        _check(lib().tsdgpu_synthesizer_create_real(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
+        create = _create if _create is not None else lib().tsdgpu_synthesizer_create_real
+        _check(create(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
         self.rows = lib().tsdgpu_synthesizer_rows(self._h)
         self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
-        self.frames_kept = self.history_len // self.rows                # P - 1
+        self.frames_kept = self.history_len // self.rows                # P - 1 (OS > 1: Q - 1, Q = ceil(K / D))
         self.hop = lib().tsdgpu_synthesizer_hop(self._h)
+
+    @classmethod
+    def oversampled(cls, taps, channels, oversample):
+        """the bank at hop D = channels / oversample, oversample in {1, 2, 4} (1: the bank and the bits of the constructor)"""
+        return cls(taps, channels, oversample, _create=lib().tsdgpu_synthesizer_create_real_oversampled)
+
+    @property
+    def phase(self):
+        """hops consumed so far, modulo `oversample` (always 0 at oversample = 1)"""
+        return lib().tsdgpu_synthesizer_get_phase(self._h)
+
+    @phase.setter
+    def phase(self, hops):
+        _check(lib().tsdgpu_synthesizer_set_phase(self._h, int(hops)))
 
     def out_count(self, frames):
         return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
 
     def step(self, u, x=None, stream=None):
         """u: (rows, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
-        x: 1-D float32 with at least F M samples, of u's kind (default: a new one); returns its first F M samples."""
+        x: 1-D float32 with at least F hop samples, of u's kind (default: a new one); returns its first F hop samples
+        (hop = M, or D = M / oversample)."""
         if _dtype_code(u) != C64 or u.ndim != 2:
             raise TsdGpuError("the real-output synthesizer takes a 2-D (channels / 2 + 1, frames) complex64 block")
         pu, ldu = _ptr2d(u, self.rows)

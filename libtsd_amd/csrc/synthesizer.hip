@@ -20,7 +20,8 @@
 // the handle's history when they lie before the step.  The last workgroup writes the new history (the last P - 1 input frames of
 // old history ++ u, per channel) into the other buffer.
 // The oversampled bank (hop D = M / OS, OS in {2, 4}) is the sibling kernel of synthesizer_os.hip; the handle and the entry points
-// below serve both.  And the real-output bank (synthesizer_real.hip: M / 2 + 1 rows into a float32 stream): x counts floats there.
+// below serve both.  And the real-output banks (synthesizer_real.hip: M / 2 + 1 rows into a float32 stream; synthesizer_real_os.hip: the
+// same at hop D): x counts floats there.
 #include "common.hpp"
 #include "bank_internal.hpp"
 #include "synthesizer_handle.hpp"
@@ -243,7 +244,8 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   int rc;
   if ((rc = bank_stage_in(u, ldu, F, rows, sz, false, F, c->in_stage, st, &du, &dldu))) return rc;
   if ((rc = stage_out(x, (size_t) n * szx, c->out_stage, &dx, &staged))) return rc;
-  if (c->real) rc = syn_real_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
+  if (c->real && c->OS > 1) rc = syn_real_os_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
+  else if (c->real) rc = syn_real_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
   else if (c->OS > 1) rc = syn_os_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
   else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
     return syn_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);

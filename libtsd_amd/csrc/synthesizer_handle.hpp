@@ -1,5 +1,6 @@
-// synthesizer_handle.hpp -- the synthesizer's handle, shared by its three kernel families: the maximally decimated bank
-// (synthesizer.hip), the oversampled one (synthesizer_os.hip) and the real-output one (synthesizer_real.hip).
+// synthesizer_handle.hpp -- the synthesizer's handle, shared by its four kernel families: the maximally decimated bank
+// (synthesizer.hip), the oversampled one (synthesizer_os.hip), the real-output one (synthesizer_real.hip) and the oversampled
+// real-output one (synthesizer_real_os.hip).
 #pragma once
 #include "polybank_host.hpp"
 
@@ -18,6 +19,10 @@ int syn_os_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int6
 
 // synthesizer_real.hip: one launch of the real-output kernel (c->real) over F frames of M / 2 + 1 rows into F M floats
 int syn_real_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st);
+
+// synthesizer_real_os.hip: one launch of the oversampled real-output kernel (c->real, c->OS in {2, 4}) over F frames of
+// M / 2 + 1 rows into F D floats; reads c->phase
+int syn_real_os_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st);
 
 // rows a step reads
 inline int syn_rows(const tsdgpu_synthesizer *c) { return c->real ? c->M / 2 + 1 : c->M; }

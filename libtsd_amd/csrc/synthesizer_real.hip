@@ -216,7 +216,8 @@ int tsdgpu_synthesizer_create_real(tsdgpu_synthesizer **out, int channels, int o
     return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: channels = %d: served are the powers of two from %d to %d", channels,
                    CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
   if (oversample != 1)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: oversample = %d: the real-output bank serves 1 only", oversample);
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: oversample = %d: this entry serves 1 only (2 and 4: synthesizer_create_real_oversampled)",
+                   oversample);
   if (ntaps > CHAN_MAX_P * channels)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
                    ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);

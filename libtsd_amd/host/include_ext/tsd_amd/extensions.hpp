@@ -110,6 +110,13 @@ sptr<FiltreGen<cfloat>> synthetiseur_polyphase(const Vecf &h, entier nb_canaux, 
 // Host or resident vectors.  The imaginary parts of rows 0 and nb_canaux / 2 are not used: any value there, a NaN included, leaves
 // the output as it is.  Served: nb_canaux a power of two in [16, 1024], K <= 16 nb_canaux; else the factory fails.
 sptr<FiltreGen<cfloat, float>> synthetiseur_polyphase_reel(const Vecf &h, entier nb_canaux);
+// The same bank oversampled by surech = OS in {1, 2, 4} (tsdgpu_synthesizer_create_real_oversampled), the way back from
+// canaliseur_polyphase_reel(h, nb_canaux, surech): a frame per hop of D = nb_canaux / OS floats, synthetiseur_polyphase(h, nb_canaux,
+// surech) on the extended block.  step(x, y): x.rows() = (nb_canaux / 2 + 1) blocks of F samples (else échec); y is resized to
+// D * F floats; x and y must not share memory.  The object carries the history (the last ceil(K / D) - 1 frames) and the phase of
+// the hop.  Served: nb_canaux as above, K <= 16 D; else the factory fails (surech < 1 included).  surech = 1 is the factory above
+// and its bits.
+sptr<FiltreGen<cfloat, float>> synthetiseur_polyphase_reel(const Vecf &h, entier nb_canaux, entier surech);
 
 // ---- device memory for resident vectors ------------------------------------------------------------
 // A vector mapped on device memory, TabT<T,1>::map(ptr, n) (tableau.hpp:1067-1077), is accepted by
