@@ -919,73 +919,71 @@ class PolyFirBank:
             pass
 
 
-class Channelizer:
-    """Polyphase analysis bank (tsdgpu_channelizer): ONE complex64 stream into `channels` = M rows, one launch per step.
-    `oversample` = OS in {1, 2, 4}: a new frame every hop D = M / OS samples (1: the maximally decimated bank).  step(x) takes
-    n = F D samples and returns the (M, F) block y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m D + D - 1:
-    the (C, n) layout FirBank / SosBank / PolyFirBank read.  For OS > 1 the state is the history and `phase`, the hops consumed
-    so far modulo OS: move both to continue a stream in a fresh handle."""
+def _empty_like(a, shape, code):
+    """a new packed array of a's kind (numpy, or torch on a's device) with the dtype of `code`"""
+    if isinstance(a, np.ndarray):
+        return np.empty(shape, np.complex64 if code == C64 else np.float32)
+    import torch
+    return a.new_empty(shape, dtype=torch.complex64 if code == C64 else torch.float32)
 
-    def __init__(self, taps, channels, oversample=1):
+
+class _PolyBank:
+    """What the four polyphase bank classes share: the handle behind one C prefix, `phase`, out_count, reset, the state, close.
+    A class says its C prefix (`_op`), what the messages call it (`_name`) and the dtype code of its 1-D stream (`_stream`; the
+    rows are complex64), and its direction says the state's dtype and shape (`_state`)."""
+    _op, _name, _stream = None, None, C64
+
+    def _fn(self, name):
+        return getattr(lib(), f"tsdgpu_{self._op}_{name}")
+
+    def _open(self, create, taps, channels, oversample, *os_arg):
+        """create(&handle, channels, *os_arg, taps, K), then what the handle says about itself"""
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
         self._h = C.c_void_p()
-        pt = t.ctypes.data if len(t) else None
-        if self.oversample == 1:
-            _check(lib().tsdgpu_channelizer_create(C.byref(self._h), self.channels, pt, len(t)))
-        else:
-            _check(lib().tsdgpu_channelizer_create_oversampled(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
-        self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
-        self.hop = lib().tsdgpu_channelizer_hop(self._h)
+        _check(create(C.byref(self._h), self.channels, *os_arg, t.ctypes.data if len(t) else None, len(t)))
+        self.rows = self._fn("rows")(self._h)
+        self.history_len = self._fn("history_len")(self._h)
+        self.hop = self._fn("hop")(self._h)
 
     @property
     def phase(self):
-        """hops consumed so far, modulo `oversample`"""
-        return lib().tsdgpu_channelizer_get_phase(self._h)
+        """hops consumed so far, modulo `oversample` (always 0 at oversample = 1)"""
+        return self._fn("get_phase")(self._h)
 
     @phase.setter
     def phase(self, hops):
-        _check(lib().tsdgpu_channelizer_set_phase(self._h, int(hops)))
+        _check(self._fn("set_phase")(self._h, int(hops)))
 
     def out_count(self, n):
-        return lib().tsdgpu_channelizer_out_count(self._h, int(n))
-
-    def step(self, x, y=None, stream=None):
-        """x: 1-D complex64 numpy array (host) or torch tensor (host or device), a whole number of hops of D samples.
-        y: (M, m) with m >= n / D, of x's kind, rows may be strided (default: a new packed one); returns its (M, n / D) view."""
-        if _dtype_code(x) != C64 or x.ndim != 1:
-            raise TsdGpuError("the channelizer takes a 1-D complex64 stream")
-        n = int(x.shape[0])
-        if y is None:
-            nout = n // self.hop
-            y = np.empty((self.channels, nout), x.dtype) if isinstance(x, np.ndarray) else x.new_empty((self.channels, nout))
-        if _dtype_code(y) != C64:
-            raise TsdGpuError("the channelizer writes complex64 rows")
-        py, ldy = _ptr2d(y, self.channels)
-        got = C.c_int64(0)
-        _check(lib().tsdgpu_channelizer_step(self._h, _ptr(x), n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
-        return y[:, : got.value]
+        """analysis: the frames n samples make; synthesis: the samples n frames make"""
+        return self._fn("out_count")(self._h, int(n))
 
     def reset(self):
-        _check(lib().tsdgpu_channelizer_reset(self._h))
+        _check(self._fn("reset")(self._h))
 
     def get_state(self, dst=None, stream=None):
-        """the last history_len = P M - D input samples, oldest first.  dst: packed numpy array or torch tensor."""
+        """The history.  Analysis: the last history_len = P M - D input samples (floats in the real bank), oldest first.
+        Synthesis: the last frames_kept input frames as a (rows, frames_kept) complex64 block, row c = channel c's last inputs,
+        oldest first.  dst: packed numpy array or torch tensor of that shape.  For oversample > 1 the state has a second part,
+        `phase`."""
+        code, shape = self._state()
         if dst is None:
-            dst = np.zeros(self.history_len, np.complex64)
-        assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == C64
-        _check(lib().tsdgpu_channelizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
+            dst = np.zeros(shape, np.complex64 if code == C64 else np.float32)
+        assert tuple(dst.shape) == shape and _dtype_code(dst) == code
+        _check(self._fn("get_state")(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
         return dst
 
     def set_state(self, hist=None, stream=None):
         if self.history_len:
-            assert tuple(hist.shape) == (self.history_len,) and _dtype_code(hist) == C64
-        _check(lib().tsdgpu_channelizer_set_state(self._h, _ptr(hist) if self.history_len else None,
-                                                  _stream_of(hist, stream) if self.history_len else stream))
+            code, shape = self._state()
+            assert tuple(hist.shape) == shape and _dtype_code(hist) == code
+        _check(self._fn("set_state")(self._h, _ptr(hist) if self.history_len else None,
+                                     _stream_of(hist, stream) if self.history_len else stream))
 
     def close(self):
         if self._h:
-            lib().tsdgpu_channelizer_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -995,7 +993,76 @@ class Channelizer:
             pass
 
 
-class RealChannelizer:
+class _AnalysisBank(_PolyBank):
+    _op = "channelizer"
+
+    def _state(self):
+        return self._stream, (self.history_len,)
+
+    def step(self, x, y=None, stream=None):
+        """x: 1-D numpy array (host) or torch tensor (host or device) of the bank's stream dtype (complex64; float32 in the real
+        bank), a whole number of hops of D = M / oversample samples (frames of M at oversample = 1).
+        y: (rows, m) complex64 with m >= n / D, of x's kind, rows may be strided (default: a new packed one); returns its
+        (rows, n / D) view."""
+        kind = "complex64" if self._stream == C64 else "float32"
+        if _dtype_code(x) != self._stream or x.ndim != 1:
+            raise TsdGpuError(f"the {self._name} takes a 1-D {kind} stream")
+        n = int(x.shape[0])
+        if y is None:
+            y = _empty_like(x, (self.rows, n // self.hop), C64)
+        if _dtype_code(y) != C64:
+            raise TsdGpuError(f"the {self._name} writes complex64 rows")
+        py, ldy = _ptr2d(y, self.rows)
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_channelizer_step(self._h, _ptr(x), n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
+        return y[:, : got.value]
+
+
+class _SynthesisBank(_PolyBank):
+    _op = "synthesizer"
+    _block = "(channels, frames)"
+
+    def _open(self, *args):
+        super()._open(*args)
+        self.frames_kept = self.history_len // self.rows                # P - 1 (OS > 1: Q - 1, Q = ceil(K / D))
+
+    def _state(self):
+        return C64, (self.rows, self.frames_kept)
+
+    def step(self, u, x=None, stream=None):
+        """u: (rows, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
+        x: 1-D of the bank's stream dtype (complex64; float32 in the real bank) with at least F D samples, D = M / oversample,
+        of u's kind (default: a new one); returns its first F D samples."""
+        kind = "complex64" if self._stream == C64 else "float32"
+        if _dtype_code(u) != C64 or u.ndim != 2:
+            raise TsdGpuError(f"the {self._name} takes a 2-D {self._block} complex64 block")
+        pu, ldu = _ptr2d(u, self.rows)
+        F = int(u.shape[1])
+        if x is None:
+            x = _empty_like(u, F * self.hop, self._stream)
+        if _dtype_code(x) != self._stream or x.ndim != 1:
+            raise TsdGpuError(f"the {self._name} writes a 1-D {kind} stream")
+        got = C.c_int64(0)
+        _check(lib().tsdgpu_synthesizer_step(self._h, pu, ldu, F, _ptr(x), int(x.shape[0]), C.byref(got), _stream_of(u, stream)))
+        return x[: got.value]
+
+
+class Channelizer(_AnalysisBank):
+    """Polyphase analysis bank (tsdgpu_channelizer): ONE complex64 stream into `channels` = M rows, one launch per step.
+    `oversample` = OS in {1, 2, 4}: a new frame every hop D = M / OS samples (1: the maximally decimated bank).  step(x) takes
+    n = F D samples and returns the (M, F) block y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m D + D - 1:
+    the (C, n) layout FirBank / SosBank / PolyFirBank read.  For OS > 1 the state is the history and `phase`, the hops consumed
+    so far modulo OS: move both to continue a stream in a fresh handle."""
+    _name = "channelizer"
+
+    def __init__(self, taps, channels, oversample=1):
+        if int(oversample) == 1:
+            self._open(lib().tsdgpu_channelizer_create, taps, channels, oversample)
+        else:
+            self._open(lib().tsdgpu_channelizer_create_oversampled, taps, channels, oversample, int(oversample))
+
+
+class RealChannelizer(_AnalysisBank):
     """Polyphase analysis bank for a REAL stream (tsdgpu_channelizer_create_real): ONE float32 stream into `rows` = M / 2 + 1
     complex64 rows, one launch per step.  step(x) takes n = F M floats and returns the (M / 2 + 1, F) block
     y[c, m] = sum_k h[k] x[n_m - k] exp(-2 pi i c (n_m - k) / M), n_m = m M + M - 1, c <= M / 2: the rows of Channelizer(taps, M) on
@@ -1005,166 +1072,34 @@ class RealChannelizer:
     hop D = M / OS floats, n_m = m D + D - 1: rows 0 .. M / 2 of Channelizer(taps, M, oversample=OS) on the widened stream.
     step(x) takes n = F D floats.  For OS > 1 the state is the last history_len = P M - D floats and `phase`, the hops consumed
     so far modulo OS: move both to continue a stream in a fresh handle.  The constructor itself serves oversample = 1 only."""
+    _name, _stream = "real-input channelizer", F32
 
     def __init__(self, taps, channels, oversample=1, _create=None):
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
-        self._h = C.c_void_p()
-        pt = t.ctypes.data if len(t) else None
         create = _create if _create is not None else lib().tsdgpu_channelizer_create_real
-        _check(create(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
-        self.rows = lib().tsdgpu_channelizer_rows(self._h)
-        self.history_len = lib().tsdgpu_channelizer_history_len(self._h)
-        self.hop = lib().tsdgpu_channelizer_hop(self._h)
+        self._open(create, taps, channels, oversample, int(oversample))
 
     @classmethod
     def oversampled(cls, taps, channels, oversample):
         """the bank at hop D = channels / oversample, oversample in {1, 2, 4} (1: the bank and the bits of the constructor)"""
         return cls(taps, channels, oversample, _create=lib().tsdgpu_channelizer_create_real_oversampled)
 
-    @property
-    def phase(self):
-        """hops consumed so far, modulo `oversample` (always 0 at oversample = 1)"""
-        return lib().tsdgpu_channelizer_get_phase(self._h)
 
-    @phase.setter
-    def phase(self, hops):
-        _check(lib().tsdgpu_channelizer_set_phase(self._h, int(hops)))
-
-    def out_count(self, n):
-        return lib().tsdgpu_channelizer_out_count(self._h, int(n))
-
-    def step(self, x, y=None, stream=None):
-        """x: 1-D float32 numpy array (host) or torch tensor (host or device), a whole number of hops of D = M / oversample
-        floats (frames of M at oversample = 1).
-        y: (rows, m) complex64 with m >= n / D, of x's kind, rows may be strided (default: a new packed one); returns its
-        (rows, n / D) view."""
-        if _dtype_code(x) != F32 or x.ndim != 1:
-            raise TsdGpuError("the real-input channelizer takes a 1-D float32 stream")
-        n = int(x.shape[0])
-        if y is None:
-            nout = n // self.hop
-            if isinstance(x, np.ndarray):
-                y = np.empty((self.rows, nout), np.complex64)
-            else:
-                import torch
-                y = x.new_empty((self.rows, nout), dtype=torch.complex64)
-        if _dtype_code(y) != C64:
-            raise TsdGpuError("the real-input channelizer writes complex64 rows")
-        py, ldy = _ptr2d(y, self.rows)
-        got = C.c_int64(0)
-        _check(lib().tsdgpu_channelizer_step(self._h, _ptr(x), n, py, ldy, int(y.shape[1]), C.byref(got), _stream_of(x, stream)))
-        return y[:, : got.value]
-
-    def reset(self):
-        _check(lib().tsdgpu_channelizer_reset(self._h))
-
-    def get_state(self, dst=None, stream=None):
-        """the last history_len = P M - D input floats ((P - 1) M at oversample = 1), oldest first.  dst: packed float32 numpy
-        array or torch tensor.  For oversample > 1 the state has a second part, `phase`."""
-        if dst is None:
-            dst = np.zeros(self.history_len, np.float32)
-        assert tuple(dst.shape) == (self.history_len,) and _dtype_code(dst) == F32
-        _check(lib().tsdgpu_channelizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
-        return dst
-
-    def set_state(self, hist=None, stream=None):
-        if self.history_len:
-            assert tuple(hist.shape) == (self.history_len,) and _dtype_code(hist) == F32
-        _check(lib().tsdgpu_channelizer_set_state(self._h, _ptr(hist) if self.history_len else None,
-                                                  _stream_of(hist, stream) if self.history_len else stream))
-
-    def close(self):
-        if self._h:
-            lib().tsdgpu_channelizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Synthesizer:
+class Synthesizer(_SynthesisBank):
     """Polyphase synthesis bank (tsdgpu_synthesizer), the dual of Channelizer: `channels` = M complex64 rows into ONE stream, one
     launch per step.  `oversample` = OS in {1, 2, 4}: a frame per hop of D = M / OS output samples (1: the maximally decimated
     bank).  step(u) takes the (M, F) block a Channelizer of the same `oversample` or a bank wrote and returns the F D samples
     x[p] = sum_c exp(+2 pi i c p / M) sum_m u[c, m] f[p - m D], p counted over the whole stream.  For OS > 1 the state is the
     history and `phase`, the hops consumed so far modulo OS: move both to continue a stream in a fresh handle."""
+    _name = "synthesizer"
 
     def __init__(self, taps, channels, oversample=1):
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
-        self._h = C.c_void_p()
-        pt = t.ctypes.data if len(t) else None
-        if self.oversample == 1:
-            _check(lib().tsdgpu_synthesizer_create(C.byref(self._h), self.channels, pt, len(t)))
+        if int(oversample) == 1:
+            self._open(lib().tsdgpu_synthesizer_create, taps, channels, oversample)
         else:
-            _check(lib().tsdgpu_synthesizer_create_oversampled(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
-        self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
-        self.frames_kept = self.history_len // self.channels            # P - 1 (OS > 1: Q - 1, Q = ceil(K / D))
-        self.hop = lib().tsdgpu_synthesizer_hop(self._h)
-
-    @property
-    def phase(self):
-        """hops consumed so far, modulo `oversample`"""
-        return lib().tsdgpu_synthesizer_get_phase(self._h)
-
-    @phase.setter
-    def phase(self, hops):
-        _check(lib().tsdgpu_synthesizer_set_phase(self._h, int(hops)))
-
-    def out_count(self, frames):
-        return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
-
-    def step(self, u, x=None, stream=None):
-        """u: (M, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
-        x: 1-D with at least F D samples, of u's kind (default: a new one); returns its first F D samples."""
-        if _dtype_code(u) != C64 or u.ndim != 2:
-            raise TsdGpuError("the synthesizer takes a 2-D (channels, frames) complex64 block")
-        pu, ldu = _ptr2d(u, self.channels)
-        F = int(u.shape[1])
-        if x is None:
-            x = np.empty(F * self.hop, u.dtype) if isinstance(u, np.ndarray) else u.new_empty(F * self.hop)
-        if _dtype_code(x) != C64 or x.ndim != 1:
-            raise TsdGpuError("the synthesizer writes a 1-D complex64 stream")
-        got = C.c_int64(0)
-        _check(lib().tsdgpu_synthesizer_step(self._h, pu, ldu, F, _ptr(x), int(x.shape[0]), C.byref(got), _stream_of(u, stream)))
-        return x[: got.value]
-
-    def reset(self):
-        _check(lib().tsdgpu_synthesizer_reset(self._h))
-
-    def get_state(self, dst=None, stream=None):
-        """the last P - 1 input frames as an (M, P - 1) block: row c = channel c's last inputs, oldest first.
-        dst: packed numpy array or torch tensor."""
-        shape = (self.channels, self.frames_kept)
-        if dst is None:
-            dst = np.zeros(shape, np.complex64)
-        assert tuple(dst.shape) == shape and _dtype_code(dst) == C64
-        _check(lib().tsdgpu_synthesizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
-        return dst
-
-    def set_state(self, hist=None, stream=None):
-        if self.history_len:
-            assert tuple(hist.shape) == (self.channels, self.frames_kept) and _dtype_code(hist) == C64
-        _check(lib().tsdgpu_synthesizer_set_state(self._h, _ptr(hist) if self.history_len else None,
-                                                  _stream_of(hist, stream) if self.history_len else stream))
-
-    def close(self):
-        if self._h:
-            lib().tsdgpu_synthesizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._open(lib().tsdgpu_synthesizer_create_oversampled, taps, channels, oversample, int(oversample))
 
 
-class RealSynthesizer:
+class RealSynthesizer(_SynthesisBank):
     """Polyphase synthesis bank with a REAL output (tsdgpu_synthesizer_create_real), the dual of RealChannelizer: `rows` = M / 2 + 1
     complex64 rows into ONE float32 stream, one launch per step.  step(u) takes the (M / 2 + 1, F) block a RealChannelizer or a
     bank wrote and returns the F M floats
@@ -1176,85 +1111,16 @@ class RealSynthesizer:
     extended block, the way back from RealChannelizer.oversampled.  step(u) returns F D floats.  For OS > 1 the state is the last
     frames_kept = Q - 1 input frames, Q = ceil(K / D), and `phase`, the hops consumed so far modulo OS: move both to continue a
     stream in a fresh handle.  The constructor itself serves oversample = 1 only."""
+    _name, _stream, _block = "real-output synthesizer", F32, "(channels / 2 + 1, frames)"
 
     def __init__(self, taps, channels, oversample=1, _create=None):
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        self.channels, self.K, self.oversample = int(channels), len(t), int(oversample)
-        self._h = C.c_void_p()
-        pt = t.ctypes.data if len(t) else None
         create = _create if _create is not None else lib().tsdgpu_synthesizer_create_real
-        _check(create(C.byref(self._h), self.channels, self.oversample, pt, len(t)))
-        self.rows = lib().tsdgpu_synthesizer_rows(self._h)
-        self.history_len = lib().tsdgpu_synthesizer_history_len(self._h)
-        self.frames_kept = self.history_len // self.rows                # P - 1 (OS > 1: Q - 1, Q = ceil(K / D))
-        self.hop = lib().tsdgpu_synthesizer_hop(self._h)
+        self._open(create, taps, channels, oversample, int(oversample))
 
     @classmethod
     def oversampled(cls, taps, channels, oversample):
         """the bank at hop D = channels / oversample, oversample in {1, 2, 4} (1: the bank and the bits of the constructor)"""
         return cls(taps, channels, oversample, _create=lib().tsdgpu_synthesizer_create_real_oversampled)
-
-    @property
-    def phase(self):
-        """hops consumed so far, modulo `oversample` (always 0 at oversample = 1)"""
-        return lib().tsdgpu_synthesizer_get_phase(self._h)
-
-    @phase.setter
-    def phase(self, hops):
-        _check(lib().tsdgpu_synthesizer_set_phase(self._h, int(hops)))
-
-    def out_count(self, frames):
-        return lib().tsdgpu_synthesizer_out_count(self._h, int(frames))
-
-    def step(self, u, x=None, stream=None):
-        """u: (rows, F) complex64 numpy array (host) or torch tensor (host or device), rows may be strided.
-        x: 1-D float32 with at least F hop samples, of u's kind (default: a new one); returns its first F hop samples
-        (hop = M, or D = M / oversample)."""
-        if _dtype_code(u) != C64 or u.ndim != 2:
-            raise TsdGpuError("the real-output synthesizer takes a 2-D (channels / 2 + 1, frames) complex64 block")
-        pu, ldu = _ptr2d(u, self.rows)
-        F = int(u.shape[1])
-        if x is None:
-            if isinstance(u, np.ndarray):
-                x = np.empty(F * self.hop, np.float32)
-            else:
-                import torch
-                x = u.new_empty(F * self.hop, dtype=torch.float32)
-        if _dtype_code(x) != F32 or x.ndim != 1:
-            raise TsdGpuError("the real-output synthesizer writes a 1-D float32 stream")
-        got = C.c_int64(0)
-        _check(lib().tsdgpu_synthesizer_step(self._h, pu, ldu, F, _ptr(x), int(x.shape[0]), C.byref(got), _stream_of(u, stream)))
-        return x[: got.value]
-
-    def reset(self):
-        _check(lib().tsdgpu_synthesizer_reset(self._h))
-
-    def get_state(self, dst=None, stream=None):
-        """the last P - 1 input frames as an (M / 2 + 1, P - 1) block: row c = channel c's last inputs, oldest first.
-        dst: packed complex64 numpy array or torch tensor."""
-        shape = (self.rows, self.frames_kept)
-        if dst is None:
-            dst = np.zeros(shape, np.complex64)
-        assert tuple(dst.shape) == shape and _dtype_code(dst) == C64
-        _check(lib().tsdgpu_synthesizer_get_state(self._h, _ptr(dst) if self.history_len else None, _stream_of(dst, stream)))
-        return dst
-
-    def set_state(self, hist=None, stream=None):
-        if self.history_len:
-            assert tuple(hist.shape) == (self.rows, self.frames_kept) and _dtype_code(hist) == C64
-        _check(lib().tsdgpu_synthesizer_set_state(self._h, _ptr(hist) if self.history_len else None,
-                                                  _stream_of(hist, stream) if self.history_len else stream))
-
-    def close(self):
-        if self._h:
-            lib().tsdgpu_synthesizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Rii:

@@ -19,11 +19,12 @@
 // The handle also serves the oversampled bank (hop D = M / OS, OS in {2, 4}): its kernel family is channelizer_os.hip, and the
 // entry points below count a step in hops of D samples; at OS = 1 they are what they were.  And the real-input bank
 // (channelizer_real.hip: a float32 stream into M / 2 + 1 rows; channelizer_real_os.hip at OS > 1): n and the history count floats there.
-// Shared with channelizer_os.hip and synthesizer.hip: polybank_tile.hpp (device; it says why the transform block is not in it) and
-// polybank_host.hpp (the handle: what it holds, how it is filled, launched and moved).
+// The C entry points of all four analysis families are at the end of this file; the other three files hold a kernel and its launch.
+// Shared with all seven other bank files: polybank_tile.hpp (device; it says why the transform block is not in it) and
+// polybank_host.hpp (the handle, the create path, the accessor bodies, the launch and the dispatch over M and the taps).
 #include "common.hpp"
 #include "bank_internal.hpp"
-#include "channelizer_handle.hpp"
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -123,28 +124,24 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_kernel(const cpx *__restr
   }
 }
 
-template <int R0, int NPOS, int PP>
-int chan_launch_p(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  const PolyLaunch g = polybank_geometry(c, NPOS, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_kernel<R0, NPOS, PP>, "channelizer", g.lds)) return rc;
-  hipLaunchKernelGGL((channelizer_kernel<R0, NPOS, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM, c->FP,
-                     F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy));
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0, int NPOS>
 int chan_launch(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  switch (c->P) {
-#define CHAN_CASE(PP) case PP: return chan_launch_p<R0, NPOS, PP>(c, x, y, ldy, F, st)
-    CHAN_CASE(1); CHAN_CASE(2); CHAN_CASE(3); CHAN_CASE(4); CHAN_CASE(5); CHAN_CASE(6); CHAN_CASE(7); CHAN_CASE(8);
-    CHAN_CASE(9); CHAN_CASE(10); CHAN_CASE(11); CHAN_CASE(12); CHAN_CASE(13); CHAN_CASE(14); CHAN_CASE(15); CHAN_CASE(16);
-#undef CHAN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P);
+  const int rc = polybank_radix(c->T, [&](auto r0, auto npos) {
+    return polybank_taps(c->P, [&](auto pp) {
+      constexpr int R0 = decltype(r0)::value, NPOS = decltype(npos)::value, PP = decltype(pp)::value;
+      const PolyLaunch g = polybank_geometry(c, NPOS, F);
+      return polybank_launch(c, "channelizer", channelizer_kernel<R0, NPOS, PP>, g, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy));
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P) : rc;
 }
+
+// the create entries below: (who, synthesis, real, min_M, only_os1, per_channel, at_one)
+const PolySpec CHAN_CREATE = {"channelizer_create", false, false, CHAN_MIN_M, nullptr, true, nullptr};
+const PolySpec CHAN_CREATE_REAL = {"channelizer_create_real", false, true, CHAN_REAL_MIN_M,
+                                   "served is 1 (tsdgpu_channelizer_create_real_oversampled serves 2 and 4)", true, nullptr};
+const PolySpec CHAN_CREATE_REAL_OS = {"channelizer_create_real_oversampled", false, true, CHAN_REAL_MIN_M, nullptr, false, &CHAN_CREATE_REAL};
 
 }  // namespace
 }  // namespace tsdgpu
@@ -155,42 +152,22 @@ extern "C" {
 
 int tsdgpu_channelizer_create(tsdgpu_channelizer **out, int channels, const float *taps_host, int ntaps)
 {
-  return tsdgpu_channelizer_create_oversampled(out, channels, 1, taps_host, ntaps);
+  return polybank_create(out, CHAN_CREATE, channels, 1, taps_host, ntaps);
 }
 
 int tsdgpu_channelizer_create_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
 {
-  TSD_CHECK(out != nullptr, "channelizer_create: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "channelizer_create: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "channelizer_create: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "channelizer_create: K > 0 taps required");
-  if (!chan_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: channels = %d: served are the powers of two from %d to %d", channels,
-                   CHAN_MIN_M, CHAN_MAX_M);
-  if (!chan_served_oversample(oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: oversample = %d: served are 1, 2 and 4", oversample);
-  // K <= 16 D: P OS <= 16, the register window of a position stays within 15 older samples
-  if (oversample == 1 && ntaps > CHAN_MAX_P * channels)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
-                   ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
-  if (ntaps > CHAN_MAX_P * (channels / oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED,
-                   "channelizer_create: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)", ntaps, channels,
-                   channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
-  tsdgpu_channelizer *c = new tsdgpu_channelizer();
-  const int M = channels;
-  c->OS = oversample;
-  c->D = M / oversample;
-  // g[p][s] = h[p M + M - 1 - s]; the history is the last P M - D samples of the stream
-  const int rc = polybank_init(c, "channelizer_create", M, taps_host, ntaps, [c, M](int P) { return P * M - c->D; },
-                               [M](int p, int s) { return p * M + M - 1 - s; });
-  if (rc) {
-    tsdgpu_channelizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
+  return polybank_create(out, CHAN_CREATE, channels, oversample, taps_host, ntaps);
+}
+
+int tsdgpu_channelizer_create_real(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
+  return polybank_create(out, CHAN_CREATE_REAL, channels, oversample, taps_host, ntaps);
+}
+
+int tsdgpu_channelizer_create_real_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
+  return polybank_create(out, CHAN_CREATE_REAL_OS, channels, oversample, taps_host, ntaps);
 }
 
 int64_t tsdgpu_channelizer_out_count(const tsdgpu_channelizer *c, int64_t n) { return (!c || n < 0) ? -1 : n / c->D; }
@@ -209,7 +186,7 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   TSD_CHECK(F <= y_capacity, "channelizer_step: a channel's output needs %lld samples, y_capacity is %lld", (long long) F, (long long) y_capacity);
   TSD_CHECK(ldy >= F, "channelizer_step: ldy = %lld below the %lld outputs of a channel", (long long) ldy, (long long) F);
   const size_t sz = sizeof(cpx), szx = c->real ? sizeof(float) : sizeof(cpx);
-  const int rows = chan_rows(c);
+  const int rows = polybank_rows(c);
   TSD_CHECK(!ranges_overlap(x, (size_t) n * szx, y, ((size_t) (rows - 1) * (size_t) ldy + (size_t) F) * sz),
             "channelizer_step: x and y overlap (there is no in-place form: the layouts differ)");
   hipStream_t st = (hipStream_t) stream;
@@ -223,9 +200,7 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   if (c->real && c->OS > 1) rc = chan_real_os_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
   else if (c->real) rc = chan_real_launch(c, (const float *) dx, (cpx *) dy, dldy, F, st);
   else if (c->OS > 1) rc = chan_os_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
-  else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
-    return chan_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
-  });
+  else rc = chan_launch(c, (const cpx *) dx, (cpx *) dy, dldy, F, st);
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
   c->phase = (int) ((c->phase + F) % c->OS);
@@ -233,48 +208,31 @@ int tsdgpu_channelizer_step(tsdgpu_channelizer *c, const void *x, int64_t n, voi
   return bank_finish_out(y, ldy, F, rows, sz, dy, dldy, staged, st);
 }
 
-int tsdgpu_channelizer_reset(tsdgpu_channelizer *c)
-{
-  TSD_CHECK(c != nullptr, "channelizer_reset: NULL handle");
-  if (const int rc = polybank_reset(c)) return rc;
-  c->phase = 0;
-  return TSDGPU_OK;
-}
+int tsdgpu_channelizer_reset(tsdgpu_channelizer *c) { return polybank_reset(c, "channelizer"); }
 
-int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c) { return c ? c->HW : -1; }
+int tsdgpu_channelizer_history_len(const tsdgpu_channelizer *c) { return polybank_history_len(c); }
 
-int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c) { return c ? c->D : -1; }
+int tsdgpu_channelizer_hop(const tsdgpu_channelizer *c) { return polybank_hop(c); }
 
-int tsdgpu_channelizer_get_phase(const tsdgpu_channelizer *c) { return c ? c->phase : -1; }
+int tsdgpu_channelizer_rows(const tsdgpu_channelizer *c) { return polybank_rows_of(c); }
 
-int tsdgpu_channelizer_set_phase(tsdgpu_channelizer *c, int64_t hops)
-{
-  TSD_CHECK(c != nullptr, "channelizer_set_phase: NULL handle");
-  TSD_CHECK(hops >= 0, "channelizer_set_phase: %lld hops, a negative count", (long long) hops);
-  c->phase = (int) (hops % c->OS);
-  return TSDGPU_OK;
-}
+int tsdgpu_channelizer_is_real(const tsdgpu_channelizer *c) { return polybank_is_real(c); }
+
+int tsdgpu_channelizer_get_phase(const tsdgpu_channelizer *c) { return polybank_get_phase(c); }
+
+int tsdgpu_channelizer_set_phase(tsdgpu_channelizer *c, int64_t hops) { return polybank_set_phase(c, "channelizer", hops); }
 
 int tsdgpu_channelizer_get_state(tsdgpu_channelizer *c, void *hist_dst, void *stream)
 {
-  TSD_CHECK(c != nullptr, "channelizer_get_state: NULL handle");
-  TSD_CHECK(c->HW == 0 || hist_dst != nullptr, "channelizer_get_state: NULL history buffer");
-  return polybank_copy_state(c, hist_dst, nullptr, (hipStream_t) stream);
+  return polybank_copy_state(c, "channelizer_get_state", hist_dst, nullptr, (hipStream_t) stream);
 }
 
 int tsdgpu_channelizer_set_state(tsdgpu_channelizer *c, const void *hist_src, void *stream)
 {
-  TSD_CHECK(c != nullptr, "channelizer_set_state: NULL handle");
-  TSD_CHECK(c->HW == 0 || hist_src != nullptr, "channelizer_set_state: NULL history buffer");
-  return polybank_copy_state(c, nullptr, hist_src, (hipStream_t) stream);
+  return polybank_copy_state(c, "channelizer_set_state", nullptr, hist_src, (hipStream_t) stream);
 }
 
-int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c)
-{
-  if (!c) return TSDGPU_OK;
-  polybank_release(c);
-  delete c;
-  return TSDGPU_OK;
-}
+int tsdgpu_channelizer_destroy(tsdgpu_channelizer *c) { return polybank_destroy(c); }
 
 }  // extern "C"
+

@@ -8,11 +8,10 @@ constexpr int CHAN_MIN_M = 8, CHAN_MAX_M = 1024;   // channels: a power of two i
 constexpr int CHAN_MAX_P = 16;                     // taps per hop sample: K <= 16 D, D = M / OS the hop (K <= 16 M at OS = 1)
 constexpr int CHAN_NT = 512;                       // threads of a workgroup, analysis and synthesis
 
-inline bool chan_served_channels(int M) { return M >= CHAN_MIN_M && M <= CHAN_MAX_M && (M & (M - 1)) == 0; }
+// the real banks transform at M / 2, one position per thread: M / 2 in [8, 512]
+constexpr int CHAN_REAL_MIN_M = 2 * CHAN_MIN_M;
 
-// the real-input bank transforms at M / 2, one position per thread: M / 2 in [8, 512]
-constexpr int CHAN_REAL_MIN_M = 2 * CHAN_MIN_M, CHAN_REAL_MAX_M = 1024;
-inline bool chan_real_served_channels(int M) { return M >= CHAN_REAL_MIN_M && M <= CHAN_REAL_MAX_M && (M & (M - 1)) == 0; }
+inline bool chan_served_channels(int M, int min_M) { return M >= min_M && M <= CHAN_MAX_M && (M & (M - 1)) == 0; }
 
 // oversampling OS = M / D of the analysis bank: 1 (maximally decimated), 2, 4
 inline bool chan_served_oversample(int OS) { return OS == 1 || OS == 2 || OS == 4; }

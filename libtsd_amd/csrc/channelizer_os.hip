@@ -22,7 +22,8 @@
 //  - load-ahead: where the window takes the kernel over 128 VGPRs, and with them the second workgroup of a CU, the lone workgroup
 //    asks for the next unit's samples before the transform of the current one (AHEAD below); measured, DESIGN 3.12.
 // The last workgroup writes the new history (the last P M - D samples of old history ++ x) into the other buffer.
-#include "channelizer_handle.hpp"
+// The entry points are channelizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -144,34 +145,19 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_os_kernel(const cpx *__re
   }
 }
 
-template <int R0, int NPOS, int PP, int OS>
-int chan_os_launch_p(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  const PolyLaunch g = polybank_geometry(c, NPOS, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_os_kernel<R0, NPOS, PP, OS>, "channelizer", g.lds)) return rc;
-  hipLaunchKernelGGL((channelizer_os_kernel<R0, NPOS, PP, OS>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM,
-                     c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy), c->phase);
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0, int NPOS>
-int chan_os_launch_r(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  switch (c->OS * 100 + c->P) {
-#define CHAN_CASE(OS, PP) case OS * 100 + PP: return chan_os_launch_p<R0, NPOS, PP, OS>(c, x, y, ldy, F, st)
-    CHAN_CASE(2, 1); CHAN_CASE(2, 2); CHAN_CASE(2, 3); CHAN_CASE(2, 4); CHAN_CASE(2, 5); CHAN_CASE(2, 6); CHAN_CASE(2, 7); CHAN_CASE(2, 8);
-    CHAN_CASE(4, 1); CHAN_CASE(4, 2); CHAN_CASE(4, 3); CHAN_CASE(4, 4);
-#undef CHAN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel at oversampling %d", c->P, c->OS);
-}
-
 }  // namespace
 
 int chan_os_launch(tsdgpu_channelizer *c, const cpx *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  return polybank_radix(c->M, [&](auto r0, auto npos) { return chan_os_launch_r<decltype(r0)::value, decltype(npos)::value>(c, x, y, ldy, F, st); });
+  const int rc = polybank_radix(c->T, [&](auto r0, auto npos) {
+    return polybank_os_taps(c->OS, c->P, [&](auto pp, auto os) {
+      constexpr int R0 = decltype(r0)::value, NPOS = decltype(npos)::value, PP = decltype(pp)::value, OS = decltype(os)::value;
+      const PolyLaunch g = polybank_geometry(c, NPOS, F);
+      return polybank_launch(c, "channelizer", channelizer_os_kernel<R0, NPOS, PP, OS>, g, st, x, y, ldy, c->d_tab, c->d_tw, c->M, c->lgM, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy), c->phase);
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel at oversampling %d", c->P, c->OS) : rc;
 }
 
 }  // namespace tsdgpu

@@ -15,19 +15,12 @@
 //  - store: the channel-major read-back untangles rows 0 .. N - 1 on the way out (store_rows_real); row N, the Nyquist row,
 //    comes from Z[0] alone in a small pass of its own.  Rows 0 and N are written with an imaginary part of exactly 0.
 // The history is the last (P - 1) M FLOAT samples; the last workgroup writes the new one into the other buffer.
-#include "common.hpp"
-#include "bank_internal.hpp"
-#include "channelizer_handle.hpp"
+// The entry points are channelizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
 namespace {
-
-// x as complex positions: 8-B loads where the stream is 8-B aligned (xal), two 4-B loads where not
-__device__ __forceinline__ cpx load_pair(const float *__restrict__ p, int xal)
-{
-  return xal ? *reinterpret_cast<const cpx *>(p) : make_float2(p[0], p[1]);
-}
 
 // R0 in {16, 8, 4, 2}: N = R0 16^a >= 16 through s16::transform; R0 = 0: N = 8 through s16::dft8.  One position per thread.
 // N, lgN, FP: the transform length M / 2 and its LDS pitch.  gt: P rows of M taps; TW: W_N^i, i < N / 16; WM: W_M^c, c <= N.
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_real_kernel(const float *
       cpx *dst = img + (r * 16 + 8 * h) * FP + s16::pad(s);
       // v_2s[f0 + i] + i v_2s+1[f0 + i] = sum_p g[p] frame(i - p), lane by lane, oldest sample first
 #pragma unroll
-      for (int i = 0; i < 8; i++) dst[i * FP] = window_chain_pair<PP>(g, prev, cur, i);
+      for (int i = 0; i < 8; i++) dst[i * FP] = window_chain_pair<PP, 1>(g, prev, cur, i);
       window_shift<PW>(prev, cur);
     }
     __syncthreads();
@@ -114,79 +107,20 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_real_kernel(const float *
   }
 }
 
-template <int R0, int PP>
-int rchan_launch_p(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  const int N = c->M / 2;
-  const PolyLaunch g = polybank_geometry(c->cus, N, c->lgM - 1, c->FP, 1, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_real_kernel<R0, PP>, "channelizer", g.lds)) return rc;
-  hipLaunchKernelGGL((channelizer_real_kernel<R0, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->d_tw2, N,
-                     c->lgM - 1, c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy),
-                     (int) (((uintptr_t) x & 7) == 0));
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0> int rchan_launch(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  switch (c->P) {
-#define RCHAN_CASE(PP) case PP: return rchan_launch_p<R0, PP>(c, x, y, ldy, F, st)
-    RCHAN_CASE(1); RCHAN_CASE(2); RCHAN_CASE(3); RCHAN_CASE(4); RCHAN_CASE(5); RCHAN_CASE(6); RCHAN_CASE(7); RCHAN_CASE(8);
-    RCHAN_CASE(9); RCHAN_CASE(10); RCHAN_CASE(11); RCHAN_CASE(12); RCHAN_CASE(13); RCHAN_CASE(14); RCHAN_CASE(15); RCHAN_CASE(16);
-#undef RCHAN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P);
-}
-
 }  // namespace
 
 int chan_real_launch(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  // (M / 2 <= 512: one position per thread at every served M)
-  return polybank_radix(c->M / 2, [&](auto r0, auto) { return rchan_launch<decltype(r0)::value>(c, x, y, ldy, F, st); });
+  // (T = M / 2 <= 512: one position per thread at every served M)
+  const int rc = polybank_radix(c->T, [&](auto r0, auto) {
+    return polybank_taps(c->P, [&](auto pp) {
+      constexpr int R0 = decltype(r0)::value, PP = decltype(pp)::value;
+      const PolyLaunch g = polybank_geometry(c, 1, F);
+      return polybank_launch(c, "channelizer", channelizer_real_kernel<R0, PP>, g, st, x, y, ldy, c->d_tab, c->d_tw, c->d_tw2, c->T, c->lgT, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy), stream_aligned(x));
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel", c->P) : rc;
 }
 
 }  // namespace tsdgpu
-
-using namespace tsdgpu;
-
-extern "C" {
-
-int tsdgpu_channelizer_create_real(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
-{
-  TSD_CHECK(out != nullptr, "channelizer_create_real: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "channelizer_create_real: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "channelizer_create_real: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "channelizer_create_real: K > 0 taps required");
-  if (!chan_real_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: channels = %d: served are the powers of two from %d to %d", channels,
-                   CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
-  if (oversample != 1)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: oversample = %d: served is 1 (tsdgpu_channelizer_create_real_oversampled serves 2 and 4)",
-                   oversample);
-  if (ntaps > CHAN_MAX_P * channels)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
-                   ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
-  tsdgpu_channelizer *c = new tsdgpu_channelizer();
-  const int M = channels;
-  c->real = true;
-  c->OS = 1;
-  c->D = M;
-  c->hist_elem = sizeof(float);
-  // g[p][s] = h[p M + M - 1 - s]; the history is the last (P - 1) M floats of the stream; the transform runs at M / 2
-  const int rc = polybank_init(c, "channelizer_create_real", M, taps_host, ntaps, [M](int P) { return (P - 1) * M; },
-                               [M](int p, int s) { return p * M + M - 1 - s; }, 0, M / 2);
-  if (rc) {
-    tsdgpu_channelizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
-}
-
-int tsdgpu_channelizer_rows(const tsdgpu_channelizer *c) { return c ? chan_rows(c) : -1; }
-
-int tsdgpu_channelizer_is_real(const tsdgpu_channelizer *c) { return c ? (int) c->real : -1; }
-
-}  // extern "C"

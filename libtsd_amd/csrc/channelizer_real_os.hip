@@ -17,19 +17,12 @@
 //  - load-ahead: where the registers cost the second workgroup of a CU anyway, the lone workgroup asks for the next unit's
 //    pairs before the transform of the current one (AHEAD below); measured, DESIGN 3.16.
 // The last workgroup writes the new history (the last P M - D floats of old history ++ x) into the other buffer.
-#include "common.hpp"
-#include "bank_internal.hpp"
-#include "channelizer_handle.hpp"
+// The entry points are channelizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
 namespace {
-
-// x as complex positions: 8-B loads where the stream is 8-B aligned (xal), two 4-B loads where not
-__device__ __forceinline__ cpx load_pair(const float *__restrict__ p, int xal)
-{
-  return xal ? *reinterpret_cast<const cpx *>(p) : make_float2(p[0], p[1]);
-}
 
 // R0, N, lgN, FP, gt, TW, WM as channelizer_real_kernel; PP = P; OS the oversampling: PP OS <= 16, the window stays within 15
 // older pairs.  oh, nh: the history as P N - D2 pairs.
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_real_os_kernel(const floa
       cpx *dst = img + (r * 16 + 8 * h) * FP;
       // v_2s[f0 + i] + i v_2s+1[f0 + i] = sum_p g[p] frame(i - p OS), lane by lane, oldest sample first
 #pragma unroll
-      for (int i = 0; i < 8; i++) dst[i * FP + slot[i & (OS - 1)]] = window_chain_pair_os<PP, OS>(g, prev, cur, i);
+      for (int i = 0; i < 8; i++) dst[i * FP + slot[i & (OS - 1)]] = window_chain_pair<PP, OS>(g, prev, cur, i);
       window_shift<PW>(prev, cur);
     }
     if (AHEAD && it + 1 < per) {                                  // (nothing is read for a unit the sub-run does not have)
@@ -141,78 +134,21 @@ __global__ __launch_bounds__(CHAN_NT) void channelizer_real_os_kernel(const floa
   }
 }
 
-template <int R0, int PP, int OS>
-int rchan_os_launch_p(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  const int N = c->M / 2;
-  const PolyLaunch g = polybank_geometry(c->cus, N, c->lgM - 1, c->FP, 1, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) channelizer_real_os_kernel<R0, PP, OS>, "channelizer", g.lds)) return rc;
-  hipLaunchKernelGGL((channelizer_real_os_kernel<R0, PP, OS>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, x, y, ldy, c->d_tab, c->d_tw, c->d_tw2,
-                     N, c->lgM - 1, c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy),
-                     (int) (((uintptr_t) x & 7) == 0), c->phase);
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0> int rchan_os_launch(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
-{
-  switch (c->OS * 100 + c->P) {
-#define RCHAN_CASE(OS, PP) case OS * 100 + PP: return rchan_os_launch_p<R0, PP, OS>(c, x, y, ldy, F, st)
-    RCHAN_CASE(2, 1); RCHAN_CASE(2, 2); RCHAN_CASE(2, 3); RCHAN_CASE(2, 4); RCHAN_CASE(2, 5); RCHAN_CASE(2, 6); RCHAN_CASE(2, 7); RCHAN_CASE(2, 8);
-    RCHAN_CASE(4, 1); RCHAN_CASE(4, 2); RCHAN_CASE(4, 3); RCHAN_CASE(4, 4);
-#undef RCHAN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel at oversampling %d", c->P, c->OS);
-}
-
 }  // namespace
 
 int chan_real_os_launch(tsdgpu_channelizer *c, const float *x, cpx *y, int64_t ldy, int64_t F, hipStream_t st)
 {
-  // (M / 2 <= 512: one position per thread at every served M)
-  return polybank_radix(c->M / 2, [&](auto r0, auto) { return rchan_os_launch<decltype(r0)::value>(c, x, y, ldy, F, st); });
+  // (T = M / 2 <= 512: one position per thread at every served M)
+  const int rc = polybank_radix(c->T, [&](auto r0, auto) {
+    return polybank_os_taps(c->OS, c->P, [&](auto pp, auto os) {
+      constexpr int R0 = decltype(r0)::value, PP = decltype(pp)::value, OS = decltype(os)::value;
+      const PolyLaunch g = polybank_geometry(c, 1, F);
+      return polybank_launch(c, "channelizer", channelizer_real_os_kernel<R0, PP, OS>, g, st, x, y, ldy, c->d_tab, c->d_tw, c->d_tw2, c->T, c->lgT,
+                             c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(y, ldy),
+                             stream_aligned(x), c->phase);
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_step: %d taps per channel at oversampling %d", c->P, c->OS) : rc;
 }
 
 }  // namespace tsdgpu
-
-using namespace tsdgpu;
-
-extern "C" {
-
-int tsdgpu_channelizer_create_real_oversampled(tsdgpu_channelizer **out, int channels, int oversample, const float *taps_host, int ntaps)
-{
-  TSD_CHECK(out != nullptr, "channelizer_create_real_oversampled: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "channelizer_create_real_oversampled: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "channelizer_create_real_oversampled: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "channelizer_create_real_oversampled: K > 0 taps required");
-  if (!chan_real_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real_oversampled: channels = %d: served are the powers of two from %d to %d",
-                   channels, CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
-  if (!chan_served_oversample(oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "channelizer_create_real_oversampled: oversample = %d: served are 1, 2 and 4", oversample);
-  // K <= 16 D: P OS <= 16, the register window of a position stays within 15 older pairs
-  if (ntaps > CHAN_MAX_P * (channels / oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED,
-                   "channelizer_create_real_oversampled: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)",
-                   ntaps, channels, channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
-  // the maximally decimated real bank: its own handle, kernel and bits
-  if (oversample == 1) return tsdgpu_channelizer_create_real(out, channels, 1, taps_host, ntaps);
-  tsdgpu_channelizer *c = new tsdgpu_channelizer();
-  const int M = channels;
-  c->real = true;
-  c->OS = oversample;
-  c->D = M / oversample;
-  c->hist_elem = sizeof(float);
-  // g[p][s] = h[p M + M - 1 - s]; the history is the last P M - D floats of the stream; the transform runs at M / 2
-  const int rc = polybank_init(c, "channelizer_create_real_oversampled", M, taps_host, ntaps, [c, M](int P) { return P * M - c->D; },
-                               [M](int p, int s) { return p * M + M - 1 - s; }, 0, M / 2);
-  if (rc) {
-    tsdgpu_channelizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
-}
-
-}  // extern "C"

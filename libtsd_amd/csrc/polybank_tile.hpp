@@ -1,9 +1,9 @@
-// polybank_tile.hpp -- the device side the polyphase banks share (channelizer.hip, channelizer_os.hip, synthesizer.hip,
-// synthesizer_os.hip): a
-// workgroup of CHAN_NT threads, R = CHAN_NT / M sub-runs of 16-frame units, one LDS image of 16 R frames at pitch FP
-// (channelizer_internal.hpp).  Here are the thread's place in that tile, the channel-major read-back of the two analysis banks,
-// the real banks' untangling (channelizer_real.hip) and tangling (synthesizer_real.hip) steps, and the register window of a
-// position with its fma chains.  Where a bank's samples come from and where its frames go stays in
+// polybank_tile.hpp -- the device side the eight polyphase banks share (channelizer{,_os,_real,_real_os}.hip and
+// synthesizer{,_os,_real,_real_os}.hip): a workgroup of CHAN_NT threads, R = CHAN_NT / T sub-runs of 16-frame units (T the
+// transform length: M, or M / 2 in the real banks), one LDS image of 16 R frames at pitch FP (channelizer_internal.hpp).  Here are
+// the thread's place in that tile, the channel-major read-back of the analysis banks, the real banks' untangling
+// (channelizer_real{,_os}.hip) and tangling (synthesizer_real{,_os}.hip) steps with the pair load and store of their float stream,
+// and the register window of a position with its fma chains.  Where a bank's samples come from and where its frames go stays in
 // its own file, and so does the in-LDS transform of the tile (the R0 == 0 / s16::transform block): the files are built with
 // -ffp-contract=fast, and behind a function the twiddle products of that block fuse differently and give other bits.
 #pragma once
@@ -121,7 +121,12 @@ __device__ __forceinline__ void tangle_store(cpx *zc, cpx *zn, cpx a, cpx b, cpx
 __device__ __forceinline__ cpx tangle_edge(cpx u0, cpx un) { return make_float2(u0.x - un.x, u0.x + un.x); }
 __device__ __forceinline__ cpx tangle_mid(cpx um) { return make_float2(-2.f * um.y, 2.f * um.x); }
 
-// two neighbouring real samples of a float stream: one 8-B store where the stream is 8-B aligned (xal), two 4-B stores where not
+// two neighbouring real samples of a float stream as one complex position: one 8-B load where the stream is 8-B aligned (xal), two
+// 4-B loads where not; and the store alike
+__device__ __forceinline__ cpx load_pair(const float *__restrict__ p, int xal)
+{
+  return xal ? *reinterpret_cast<const cpx *>(p) : make_float2(p[0], p[1]);
+}
 __device__ __forceinline__ void store_pair(float *__restrict__ p, cpx v, int xal)
 {
   if (xal) *reinterpret_cast<cpx *>(p) = v;
@@ -146,28 +151,11 @@ __device__ __forceinline__ cpx window_chain(const float (&g)[PP], const cpx (&pr
   return make_float2(ar, ai);
 }
 
-// The same chain at OS = 1 for a position that holds two real samples (.x, .y) with a tap set each: g[p].x on the .x lane,
-// g[p].y on the .y lane (the real-input bank, channelizer_real.hip).
-template <int PP>
-__device__ __forceinline__ cpx window_chain_pair(const cpx (&g)[PP], const cpx (&prev)[PP > 1 ? PP - 1 : 1], const cpx (&cur)[8], int i)
-{
-  constexpr int PW = PP - 1;
-  float ar = 0.f, ai = 0.f;
-#pragma unroll
-  for (int p = PP - 1; p >= 0; p--) {
-    const int k = i - p;
-    const cpx w = k >= 0 ? cur[k >= 0 ? k : 0] : prev[k < 0 ? PW + k : 0];
-    ar = fmaf(g[p].x, w.x, ar);
-    ai = fmaf(g[p].y, w.y, ai);
-  }
-  return make_float2(ar, ai);
-}
-
-// The pair chain where frames overlap (the oversampled real-input bank, channelizer_real_os.hip): the position's pairs lie D
-// apart and the chain takes every OS-th, as window_chain<PP, OS> does, with the two tap sets of window_chain_pair.
+// The same chain for a position that holds two real samples (.x, .y) with a tap set each: g[p].x on the .x lane, g[p].y on the
+// .y lane (the four real banks; OS > 1 in channelizer_real_os.hip alone, where the position's pairs lie D apart and the chain takes
+// every OS-th).  Not one template with window_chain over the tap type: that reorders channelizer_real's instructions.
 template <int PP, int OS>
-__device__ __forceinline__ cpx window_chain_pair_os(const cpx (&g)[PP], const cpx (&prev)[PP > 1 ? (PP - 1) * OS : 1], const cpx (&cur)[8],
-                                                    int i)
+__device__ __forceinline__ cpx window_chain_pair(const cpx (&g)[PP], const cpx (&prev)[PP > 1 ? (PP - 1) * OS : 1], const cpx (&cur)[8], int i)
 {
   constexpr int PW = (PP - 1) * OS;
   float ar = 0.f, ai = 0.f;

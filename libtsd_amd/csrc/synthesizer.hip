@@ -21,10 +21,11 @@
 // old history ++ u, per channel) into the other buffer.
 // The oversampled bank (hop D = M / OS, OS in {2, 4}) is the sibling kernel of synthesizer_os.hip; the handle and the entry points
 // below serve both.  And the real-output banks (synthesizer_real.hip: M / 2 + 1 rows into a float32 stream; synthesizer_real_os.hip: the
-// same at hop D): x counts floats there.
+// same at hop D): x counts floats there.  The C entry points of all four synthesis families are at the end of this file; the other
+// three files hold a kernel and its launch.
 #include "common.hpp"
 #include "bank_internal.hpp"
-#include "synthesizer_handle.hpp"
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -148,28 +149,24 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_kernel(const cpx *__restr
   }
 }
 
-template <int R0, int NPOS, int PP>
-int syn_launch_p(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
-{
-  const PolyLaunch g = polybank_geometry(c, NPOS, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) synthesizer_kernel<R0, NPOS, PP>, "synthesizer", g.lds)) return rc;
-  hipLaunchKernelGGL((synthesizer_kernel<R0, NPOS, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, u, ldu, x, c->d_tab, c->d_tw, c->M, c->lgM, c->FP,
-                     F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu));
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0, int NPOS>
 int syn_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
 {
-  switch (c->P) {
-#define SYN_CASE(PP) case PP: return syn_launch_p<R0, NPOS, PP>(c, u, ldu, x, F, st)
-    SYN_CASE(1); SYN_CASE(2); SYN_CASE(3); SYN_CASE(4); SYN_CASE(5); SYN_CASE(6); SYN_CASE(7); SYN_CASE(8);
-    SYN_CASE(9); SYN_CASE(10); SYN_CASE(11); SYN_CASE(12); SYN_CASE(13); SYN_CASE(14); SYN_CASE(15); SYN_CASE(16);
-#undef SYN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per channel", c->P);
+  const int rc = polybank_radix(c->T, [&](auto r0, auto npos) {
+    return polybank_taps(c->P, [&](auto pp) {
+      constexpr int R0 = decltype(r0)::value, NPOS = decltype(npos)::value, PP = decltype(pp)::value;
+      const PolyLaunch g = polybank_geometry(c, NPOS, F);
+      return polybank_launch(c, "synthesizer", synthesizer_kernel<R0, NPOS, PP>, g, st, u, ldu, x, c->d_tab, c->d_tw, c->M, c->lgM, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu));
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per channel", c->P) : rc;
 }
+
+// the create entries below: (who, synthesis, real, min_M, only_os1, per_channel, at_one)
+const PolySpec SYN_CREATE = {"synthesizer_create", true, false, CHAN_MIN_M, nullptr, true, nullptr};
+const PolySpec SYN_CREATE_REAL = {"synthesizer_create_real", true, true, CHAN_REAL_MIN_M,
+                                  "this entry serves 1 only (2 and 4: synthesizer_create_real_oversampled)", true, nullptr};
+const PolySpec SYN_CREATE_REAL_OS = {"synthesizer_create_real_oversampled", true, true, CHAN_REAL_MIN_M, nullptr, false, &SYN_CREATE_REAL};
 
 }  // namespace
 }  // namespace tsdgpu
@@ -180,43 +177,22 @@ extern "C" {
 
 int tsdgpu_synthesizer_create(tsdgpu_synthesizer **out, int channels, const float *taps_host, int ntaps)
 {
-  return tsdgpu_synthesizer_create_oversampled(out, channels, 1, taps_host, ntaps);
+  return polybank_create(out, SYN_CREATE, channels, 1, taps_host, ntaps);
 }
 
 int tsdgpu_synthesizer_create_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
 {
-  TSD_CHECK(out != nullptr, "synthesizer_create: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "synthesizer_create: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "synthesizer_create: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "synthesizer_create: K > 0 taps required");
-  if (!chan_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: channels = %d: served are the powers of two from %d to %d", channels,
-                   CHAN_MIN_M, CHAN_MAX_M);
-  if (!chan_served_oversample(oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: oversample = %d: served are 1, 2 and 4", oversample);
-  if (oversample == 1 && ntaps > CHAN_MAX_P * channels)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
-                   ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
-  // K <= 16 D: Q <= 16, the register window of a position stays within 15 older frames
-  if (ntaps > CHAN_MAX_P * (channels / oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED,
-                   "synthesizer_create: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)", ntaps, channels,
-                   channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
-  tsdgpu_synthesizer *c = new tsdgpu_synthesizer();
-  const int M = channels, D = M / oversample;
-  c->OS = oversample;
-  c->D = D;
-  // Q = ceil(K / D) rows (OS = 1: P = ceil(K / M)), row j position r taking f[j D + (r mod D)] (OS = 1: f[j M + r]); the history is
-  // the last Q - 1 input frames
-  const int rc = polybank_init(c, "synthesizer_create", M, taps_host, ntaps, [M](int P) { return (P - 1) * M; },
-                               [D](int p, int r) { return p * D + r % D; }, (ntaps + D - 1) / D);
-  if (rc) {
-    tsdgpu_synthesizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
+  return polybank_create(out, SYN_CREATE, channels, oversample, taps_host, ntaps);
+}
+
+int tsdgpu_synthesizer_create_real(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
+  return polybank_create(out, SYN_CREATE_REAL, channels, oversample, taps_host, ntaps);
+}
+
+int tsdgpu_synthesizer_create_real_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
+{
+  return polybank_create(out, SYN_CREATE_REAL_OS, channels, oversample, taps_host, ntaps);
 }
 
 int64_t tsdgpu_synthesizer_out_count(const tsdgpu_synthesizer *c, int64_t frames) { return (!c || frames < 0) ? -1 : frames * c->D; }
@@ -233,7 +209,7 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   TSD_CHECK(n <= x_capacity, "synthesizer_step: the output needs %lld samples, x_capacity is %lld", (long long) n, (long long) x_capacity);
   TSD_CHECK(ldu >= F, "synthesizer_step: ldu = %lld below the %lld inputs of a channel", (long long) ldu, (long long) F);
   const size_t sz = sizeof(cpx), szx = c->real ? sizeof(float) : sizeof(cpx);
-  const int rows = syn_rows(c);
+  const int rows = polybank_rows(c);
   TSD_CHECK(!ranges_overlap(x, (size_t) n * szx, u, ((size_t) (rows - 1) * (size_t) ldu + (size_t) F) * sz),
             "synthesizer_step: u and x overlap (there is no in-place form: the layouts differ)");
   hipStream_t st = (hipStream_t) stream;
@@ -247,9 +223,7 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   if (c->real && c->OS > 1) rc = syn_real_os_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
   else if (c->real) rc = syn_real_launch(c, (const cpx *) du, dldu, (float *) dx, F, st);
   else if (c->OS > 1) rc = syn_os_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
-  else rc = polybank_radix(c->M, [&](auto r0, auto npos) {
-    return syn_launch<decltype(r0)::value, decltype(npos)::value>(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
-  });
+  else rc = syn_launch(c, (const cpx *) du, dldu, (cpx *) dx, F, st);
   if (rc) return rc;
   if (c->HW) c->cur ^= 1;
   c->phase = (int) ((c->phase + F) % c->OS);
@@ -257,48 +231,30 @@ int tsdgpu_synthesizer_step(tsdgpu_synthesizer *c, const void *u, int64_t ldu, i
   return finish_out(x, (size_t) n * szx, dx, staged, st);
 }
 
-int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *c)
-{
-  TSD_CHECK(c != nullptr, "synthesizer_reset: NULL handle");
-  if (const int rc = polybank_reset(c)) return rc;
-  c->phase = 0;
-  return TSDGPU_OK;
-}
+int tsdgpu_synthesizer_reset(tsdgpu_synthesizer *c) { return polybank_reset(c, "synthesizer"); }
 
-int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *c) { return c ? c->HW : -1; }
+int tsdgpu_synthesizer_history_len(const tsdgpu_synthesizer *c) { return polybank_history_len(c); }
 
-int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *c) { return c ? c->D : -1; }
+int tsdgpu_synthesizer_hop(const tsdgpu_synthesizer *c) { return polybank_hop(c); }
 
-int tsdgpu_synthesizer_get_phase(const tsdgpu_synthesizer *c) { return c ? c->phase : -1; }
+int tsdgpu_synthesizer_rows(const tsdgpu_synthesizer *c) { return polybank_rows_of(c); }
 
-int tsdgpu_synthesizer_set_phase(tsdgpu_synthesizer *c, int64_t hops)
-{
-  TSD_CHECK(c != nullptr, "synthesizer_set_phase: NULL handle");
-  TSD_CHECK(hops >= 0, "synthesizer_set_phase: %lld hops, a negative count", (long long) hops);
-  c->phase = (int) (hops % c->OS);
-  return TSDGPU_OK;
-}
+int tsdgpu_synthesizer_is_real(const tsdgpu_synthesizer *c) { return polybank_is_real(c); }
+
+int tsdgpu_synthesizer_get_phase(const tsdgpu_synthesizer *c) { return polybank_get_phase(c); }
+
+int tsdgpu_synthesizer_set_phase(tsdgpu_synthesizer *c, int64_t hops) { return polybank_set_phase(c, "synthesizer", hops); }
 
 int tsdgpu_synthesizer_get_state(tsdgpu_synthesizer *c, void *hist_dst, void *stream)
 {
-  TSD_CHECK(c != nullptr, "synthesizer_get_state: NULL handle");
-  TSD_CHECK(c->HW == 0 || hist_dst != nullptr, "synthesizer_get_state: NULL history buffer");
-  return polybank_copy_state(c, hist_dst, nullptr, (hipStream_t) stream);
+  return polybank_copy_state(c, "synthesizer_get_state", hist_dst, nullptr, (hipStream_t) stream);
 }
 
 int tsdgpu_synthesizer_set_state(tsdgpu_synthesizer *c, const void *hist_src, void *stream)
 {
-  TSD_CHECK(c != nullptr, "synthesizer_set_state: NULL handle");
-  TSD_CHECK(c->HW == 0 || hist_src != nullptr, "synthesizer_set_state: NULL history buffer");
-  return polybank_copy_state(c, nullptr, hist_src, (hipStream_t) stream);
+  return polybank_copy_state(c, "synthesizer_set_state", nullptr, hist_src, (hipStream_t) stream);
 }
 
-int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *c)
-{
-  if (!c) return TSDGPU_OK;
-  polybank_release(c);
-  delete c;
-  return TSDGPU_OK;
-}
+int tsdgpu_synthesizer_destroy(tsdgpu_synthesizer *c) { return polybank_destroy(c); }
 
 }  // extern "C"

@@ -19,7 +19,8 @@
 //  - a hop's D outputs are the threads floor(r / D) = (phase + q) mod OS of the sub-run: D contiguous samples, 512 B from D = 64.
 // OS is a launch argument, not a template parameter: the instantiations are those of synthesizer_kernel, <R0, NPOS, Q>.
 // The last workgroup writes the new history (the last Q - 1 input frames of old history ++ u, per channel) into the other buffer.
-#include "synthesizer_handle.hpp"
+// The entry points are synthesizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -148,36 +149,21 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_os_kernel(const cpx *__re
   }
 }
 
-template <int R0, int NPOS, int QQ>
-int syn_os_launch_q(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
-{
-  const PolyLaunch g = polybank_geometry(c, NPOS, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) synthesizer_os_kernel<R0, NPOS, QQ>, "synthesizer", g.lds)) return rc;
-  hipLaunchKernelGGL((synthesizer_os_kernel<R0, NPOS, QQ>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, u, ldu, x, c->d_tab, c->d_tw, c->M, c->lgM,
-                     c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu),
-                     c->OS == 2 ? 1 : 2, c->phase);
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0, int NPOS>
-int syn_os_launch_r(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
-{
-  switch (c->P) {
-#define SYN_CASE(QQ) case QQ: return syn_os_launch_q<R0, NPOS, QQ>(c, u, ldu, x, F, st)
-    SYN_CASE(1); SYN_CASE(2); SYN_CASE(3); SYN_CASE(4); SYN_CASE(5); SYN_CASE(6); SYN_CASE(7); SYN_CASE(8);
-    SYN_CASE(9); SYN_CASE(10); SYN_CASE(11); SYN_CASE(12); SYN_CASE(13); SYN_CASE(14); SYN_CASE(15); SYN_CASE(16);
-#undef SYN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per hop sample at oversampling %d", c->P, c->OS);
-}
-
 }  // namespace
 
 int syn_os_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, cpx *x, int64_t F, hipStream_t st)
 {
   if (c->OS != 2 && c->OS != 4) return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: oversampling %d", c->OS);
-  return polybank_radix(c->M, [&](auto r0, auto npos) { return syn_os_launch_r<decltype(r0)::value, decltype(npos)::value>(c, u, ldu, x, F, st); });
+  const int rc = polybank_radix(c->T, [&](auto r0, auto npos) {
+    return polybank_taps(c->P, [&](auto qq) {
+      constexpr int R0 = decltype(r0)::value, NPOS = decltype(npos)::value, QQ = decltype(qq)::value;
+      const PolyLaunch g = polybank_geometry(c, NPOS, F);
+      return polybank_launch(c, "synthesizer", synthesizer_os_kernel<R0, NPOS, QQ>, g, st, u, ldu, x, c->d_tab, c->d_tw, c->M, c->lgM, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu), c->OS == 2 ? 1 : 2,
+                             c->phase);
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per hop sample at oversampling %d", c->P, c->OS) : rc;
 }
 
 }  // namespace tsdgpu

@@ -20,9 +20,8 @@
 //    x[f M + 2 s + 1].
 // The halo unit per sub-run, the history and the launch are synthesizer_kernel's.  The history is the last P - 1 input frames as
 // a packed (N + 1, P - 1) block, the samples as the caller gave them.
-#include "common.hpp"
-#include "bank_internal.hpp"
-#include "synthesizer_handle.hpp"
+// The entry points are synthesizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_real_kernel(const cpx *__
         // x[(f0 + i) M + 2 s] + i x[(f0 + i) M + 2 s + 1] = sum_j g[j] frame(i - j), lane by lane, oldest frame first
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          const cpx v = window_chain_pair<PP>(g, prev, cur, i);
+          const cpx v = window_chain_pair<PP, 1>(g, prev, cur, i);
           if (f0 + i < F) store_pair(dst + (int64_t) i * (2 * N), v, xal);
         }
       }
@@ -167,78 +166,20 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_real_kernel(const cpx *__
   }
 }
 
-template <int R0, int PP>
-int rsyn_launch_p(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
-{
-  const int N = c->M / 2;
-  const PolyLaunch g = polybank_geometry(c->cus, N, c->lgM - 1, c->FP, 1, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) synthesizer_real_kernel<R0, PP>, "synthesizer", g.lds)) return rc;
-  hipLaunchKernelGGL((synthesizer_real_kernel<R0, PP>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, u, ldu, x, c->d_tab, c->d_tw, c->d_tw2, N,
-                     c->lgM - 1, c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu),
-                     (int) (((uintptr_t) x & 7) == 0));
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0> int rsyn_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
-{
-  switch (c->P) {
-#define RSYN_CASE(PP) case PP: return rsyn_launch_p<R0, PP>(c, u, ldu, x, F, st)
-    RSYN_CASE(1); RSYN_CASE(2); RSYN_CASE(3); RSYN_CASE(4); RSYN_CASE(5); RSYN_CASE(6); RSYN_CASE(7); RSYN_CASE(8);
-    RSYN_CASE(9); RSYN_CASE(10); RSYN_CASE(11); RSYN_CASE(12); RSYN_CASE(13); RSYN_CASE(14); RSYN_CASE(15); RSYN_CASE(16);
-#undef RSYN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per channel", c->P);
-}
-
 }  // namespace
 
 int syn_real_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
 {
-  // (M / 2 <= 512: one position per thread at every served M)
-  return polybank_radix(c->M / 2, [&](auto r0, auto) { return rsyn_launch<decltype(r0)::value>(c, u, ldu, x, F, st); });
+  // (T = M / 2 <= 512: one position per thread at every served M)
+  const int rc = polybank_radix(c->T, [&](auto r0, auto) {
+    return polybank_taps(c->P, [&](auto pp) {
+      constexpr int R0 = decltype(r0)::value, PP = decltype(pp)::value;
+      const PolyLaunch g = polybank_geometry(c, 1, F);
+      return polybank_launch(c, "synthesizer", synthesizer_real_kernel<R0, PP>, g, st, u, ldu, x, c->d_tab, c->d_tw, c->d_tw2, c->T, c->lgT, c->FP, F,
+                             g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu), stream_aligned(x));
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per channel", c->P) : rc;
 }
 
 }  // namespace tsdgpu
-
-using namespace tsdgpu;
-
-extern "C" {
-
-int tsdgpu_synthesizer_create_real(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
-{
-  TSD_CHECK(out != nullptr, "synthesizer_create_real: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "synthesizer_create_real: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "synthesizer_create_real: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "synthesizer_create_real: K > 0 taps required");
-  if (!chan_real_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: channels = %d: served are the powers of two from %d to %d", channels,
-                   CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
-  if (oversample != 1)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: oversample = %d: this entry serves 1 only (2 and 4: synthesizer_create_real_oversampled)",
-                   oversample);
-  if (ntaps > CHAN_MAX_P * channels)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real: %d taps over %d channels: served are up to %d taps per channel (%d taps)",
-                   ntaps, channels, CHAN_MAX_P, CHAN_MAX_P * channels);
-  tsdgpu_synthesizer *c = new tsdgpu_synthesizer();
-  const int M = channels;
-  c->real = true;
-  c->OS = 1;
-  c->D = M;
-  // f[j][s] = f[j M + s]; the history is the last P - 1 input frames of the M / 2 + 1 rows; the transform runs at M / 2
-  const int rc = polybank_init(c, "synthesizer_create_real", M, taps_host, ntaps, [M](int P) { return (P - 1) * (M / 2 + 1); },
-                               [M](int p, int s) { return p * M + s; }, 0, M / 2);
-  if (rc) {
-    tsdgpu_synthesizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
-}
-
-int tsdgpu_synthesizer_rows(const tsdgpu_synthesizer *c) { return c ? syn_rows(c) : -1; }
-
-int tsdgpu_synthesizer_is_real(const tsdgpu_synthesizer *c) { return c ? (int) c->real : -1; }
-
-}  // extern "C"

@@ -24,9 +24,8 @@
 // OS and the phase are launch arguments: the instantiations are synthesizer_real_kernel's, <R0, Q>.
 // The last workgroup writes the new history (the last Q - 1 input frames of old history ++ u, per row, as fed) into the other
 // buffer: a packed (N + 1, Q - 1) block.
-#include "common.hpp"
-#include "bank_internal.hpp"
-#include "synthesizer_handle.hpp"
+// The entry points are synthesizer.hip's; this file is the kernel and its launch.
+#include "polybank_host.hpp"
 #include "polybank_tile.hpp"
 
 namespace tsdgpu {
@@ -166,7 +165,7 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_real_os_kernel(const cpx 
 #pragma unroll
         for (int i = 0; i < 8; i++)
           if ((i & OSM) == sel) {
-            const cpx v = window_chain_pair<QQ>(g, prev, cur, i);
+            const cpx v = window_chain_pair<QQ, 1>(g, prev, cur, i);
             if (f0 + i < F) store_pair(dst + ((int64_t) i << lgD), v, xal);
           }
       }
@@ -176,79 +175,22 @@ __global__ __launch_bounds__(CHAN_NT) void synthesizer_real_os_kernel(const cpx 
   }
 }
 
-template <int R0, int QQ>
-int rsyn_os_launch_q(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
-{
-  const int N = c->M / 2;
-  const PolyLaunch g = polybank_geometry(c->cus, N, c->lgM - 1, c->FP, 1, F);
-  if (const int rc = polybank_lds_attr(c, (const void *) synthesizer_real_os_kernel<R0, QQ>, "synthesizer", g.lds)) return rc;
-  hipLaunchKernelGGL((synthesizer_real_os_kernel<R0, QQ>), dim3(g.grid), dim3(CHAN_NT), g.lds, st, u, ldu, x, c->d_tab, c->d_tw, c->d_tw2, N,
-                     c->lgM - 1, c->FP, F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu),
-                     (int) (((uintptr_t) x & 7) == 0), c->OS == 2 ? 1 : 2, c->phase);
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
-}
-
-template <int R0> int rsyn_os_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
-{
-  switch (c->P) {
-#define RSYN_CASE(QQ) case QQ: return rsyn_os_launch_q<R0, QQ>(c, u, ldu, x, F, st)
-    RSYN_CASE(1); RSYN_CASE(2); RSYN_CASE(3); RSYN_CASE(4); RSYN_CASE(5); RSYN_CASE(6); RSYN_CASE(7); RSYN_CASE(8);
-    RSYN_CASE(9); RSYN_CASE(10); RSYN_CASE(11); RSYN_CASE(12); RSYN_CASE(13); RSYN_CASE(14); RSYN_CASE(15); RSYN_CASE(16);
-#undef RSYN_CASE
-  }
-  return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per hop sample at oversampling %d", c->P, c->OS);
-}
-
 }  // namespace
 
 int syn_real_os_launch(tsdgpu_synthesizer *c, const cpx *u, int64_t ldu, float *x, int64_t F, hipStream_t st)
 {
   if (c->OS != 2 && c->OS != 4) return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: oversampling %d", c->OS);
-  // (M / 2 <= 512: one position per thread at every served M)
-  return polybank_radix(c->M / 2, [&](auto r0, auto) { return rsyn_os_launch<decltype(r0)::value>(c, u, ldu, x, F, st); });
+  // (T = M / 2 <= 512: one position per thread at every served M)
+  const int rc = polybank_radix(c->T, [&](auto r0, auto) {
+    return polybank_taps(c->P, [&](auto qq) {
+      constexpr int R0 = decltype(r0)::value, QQ = decltype(qq)::value;
+      const PolyLaunch g = polybank_geometry(c, 1, F);
+      return polybank_launch(c, "synthesizer", synthesizer_real_os_kernel<R0, QQ>, g, st, u, ldu, x, c->d_tab, c->d_tw, c->d_tw2, c->T, c->lgT, c->FP,
+                             F, g.per, (const cpx *) c->hist[c->cur], (cpx *) c->hist[c->cur ^ 1], rows_aligned(u, ldu), stream_aligned(x),
+                             c->OS == 2 ? 1 : 2, c->phase);
+    });
+  });
+  return rc == POLYBANK_UNSERVED ? set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_step: %d taps per hop sample at oversampling %d", c->P, c->OS) : rc;
 }
 
 }  // namespace tsdgpu
-
-using namespace tsdgpu;
-
-extern "C" {
-
-int tsdgpu_synthesizer_create_real_oversampled(tsdgpu_synthesizer **out, int channels, int oversample, const float *taps_host, int ntaps)
-{
-  TSD_CHECK(out != nullptr, "synthesizer_create_real_oversampled: out is NULL");
-  *out = nullptr;
-  TSD_CHECK(channels >= 1, "synthesizer_create_real_oversampled: channels = %d, need at least one", channels);
-  TSD_CHECK(oversample >= 1, "synthesizer_create_real_oversampled: oversample = %d, need at least one", oversample);
-  TSD_CHECK(taps_host != nullptr && ntaps >= 1, "synthesizer_create_real_oversampled: K > 0 taps required");
-  if (!chan_real_served_channels(channels))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real_oversampled: channels = %d: served are the powers of two from %d to %d",
-                   channels, CHAN_REAL_MIN_M, CHAN_REAL_MAX_M);
-  if (!chan_served_oversample(oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "synthesizer_create_real_oversampled: oversample = %d: served are 1, 2 and 4", oversample);
-  // K <= 16 D: Q <= 16, the register window of a pair stays within 15 older frames
-  if (ntaps > CHAN_MAX_P * (channels / oversample))
-    return set_err(TSDGPU_ERR_UNSUPPORTED,
-                   "synthesizer_create_real_oversampled: %d taps over %d channels at hop %d: served are up to %d taps per hop sample (%d taps)",
-                   ntaps, channels, channels / oversample, CHAN_MAX_P, CHAN_MAX_P * (channels / oversample));
-  // the maximally decimated real bank: its own handle, kernel and bits
-  if (oversample == 1) return tsdgpu_synthesizer_create_real(out, channels, 1, taps_host, ntaps);
-  tsdgpu_synthesizer *c = new tsdgpu_synthesizer();
-  const int M = channels, D = M / oversample;
-  c->real = true;
-  c->OS = oversample;
-  c->D = D;
-  // Q = ceil(K / D) rows, row j position r taking f[j D + (r mod D)]; the history is the last Q - 1 input frames of the M / 2 + 1
-  // rows; the transform runs at M / 2
-  const int rc = polybank_init(c, "synthesizer_create_real_oversampled", M, taps_host, ntaps, [M](int P) { return (P - 1) * (M / 2 + 1); },
-                               [D](int p, int r) { return p * D + r % D; }, (ntaps + D - 1) / D, M / 2);
-  if (rc) {
-    tsdgpu_synthesizer_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return TSDGPU_OK;
-}
-
-}  // extern "C"
