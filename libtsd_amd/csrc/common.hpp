@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/tsdgpu.h"
 
@@ -159,5 +160,23 @@ int fft_blu_framed_launch(const tsdgpu_fft *p, const float2 *x, int64_t pas, con
                           int64_t *rows, void *stream);
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The maps from a run-time value to a kernel's template argument, as std::integral_constants: compile-time switches, nothing
+// looked up or allocated on the way to a launch.  int_switch<A, B, ..., Z>(v, fn) calls the generic lambda fn with int_c<A>() where
+// v == A, int_c<B>() where v == B ...; Z serves every other value.  Returns what fn returns.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int V, int... Vs, typename FN> auto int_switch(int v, FN fn)
+{
+  if constexpr (sizeof...(Vs) == 0) {
+    return fn(int_c<V>());
+  } else {
+    if (v == V) return fn(int_c<V>());
+    return int_switch<Vs...>(v, fn);
+  }
+}
+// the radix of the first pass of a 2^log2n-point radix-16 Stockham transform (stockham16.hpp), 2, 4, 8 or 16, and fn(int_c<R0>())
+// for that radix
+inline int first_radix(int log2n) { return 1 << ((log2n & 3) == 0 ? 4 : (log2n & 3)); }
+template <typename FN> auto s16_radix(int r0, FN fn) { return int_switch<16, 8, 4, 2>(r0, fn); }
 
 }  // namespace tsdgpu

@@ -134,35 +134,6 @@ __device__ __forceinline__ void wave_fence()
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// n = 1024: one wave per transform, 4 transforms per workgroup, contiguous in and out.
-__global__ __launch_bounds__(256) void fft1024_rows_kernel(const cpx *__restrict__ in, cpx *__restrict__ out,
-                                                           const cpx *__restrict__ TW1, const cpx *__restrict__ TW2,
-                                                           int inverse, float scale, int ntr)
-{
-  __shared__ cpx lds[4 * w1024::LDS_ELEMS];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int tr = blockIdx.x * 4 + wv;
-  if (tr >= ntr) return;
-  cpx tw1[16], tw2[16], v[16];
-  const cpx *x = in + (size_t) tr * 1024;
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    v[r] = x[64 * r + lane];
-    if (inverse) v[r].y = -v[r].y;
-    tw1[r] = TW1[r * 64 + lane];
-    tw2[r] = TW2[r * 64 + lane];
-  }
-  w1024::forward<1>(v, lds + wv * w1024::LDS_ELEMS, lane, tw1, tw2, wave_fence);
-  cpx *y = out + (size_t) tr * 1024;
-  const int k0 = (lane >> 2) + 16 * (lane & 3);            // freq_index(lane, r) = k0 + 64*(r>>2) + 256*(r&3)
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    cpx o = cscale(v[r], scale);
-    if (inverse) o.y = -o.y;
-    y[k0 + 64 * (r >> 2) + 256 * (r & 3)] = o;
-  }
-}
-
 // ---- n = 16 .. 16384: Stockham autosort in LDS, radix 16 ---------------------------------------
 // n = R0 * 16^a with R0 in {16, 8, 4, 2}: the first pass has radix R0 and needs no twiddles,
 // every further pass is a 16-point in-register DFT (w1024::dft16).  Thread j of the n/16
@@ -1897,9 +1868,80 @@ __global__ void fftshift_kernel(const T *__restrict__ x, T *__restrict__ y, int 
 
 using namespace tsdgpu;
 
+namespace {
+
+// The dynamic tile hand-out of the persistent column kernels (fft1m_cols_kernel, fft2k_cols_kernel): ONE device counter that is
+// never reset.  Its value before the next launch is tracked here and goes into each launch as that launch's base; a launch of
+// `tiles` tiles over `grid` workgroups leaves it at base + tiles + grid (one failing pull per workgroup).
+struct TileCounter {
+  unsigned *d = nullptr;      // NULL: no counter, every pass takes its static partition
+  unsigned base = 0;          // the counter's value before the next launch (advanced once a step's launches have been accepted)
+  bool stale = false;         // a launch that used the counter failed: zero it again before the next use
+  unsigned next = 0;          // between begin() and commit(): the base after this step
+  bool used = false;          //   ... and whether a pass of it took the counter
+
+  // a pass of a step; `on`: it runs on a kernel that has the hand-out.  begin() fills ctr (NULL: the static partition) and base
+  struct Pass {
+    int64_t tiles = 0;
+    int grid = 0;
+    bool on = true;
+    unsigned *ctr = nullptr;
+    unsigned base = 0;
+  };
+
+  void alloc()
+  {
+    if (hipMalloc((void **) &d, 256) != hipSuccess || hipMemset(d, 0, 256) != hipSuccess) {
+      (void) hipGetLastError();
+      d = nullptr;                                         // (the static partition then)
+    }
+  }
+  void release()
+  {
+    if (d) (void) hipFree(d);
+  }
+
+  // The passes of one step, in launch order.  A pass is handed out dynamically when there is a counter, TSDGPU_FFT_DYN is not 0,
+  // every workgroup gets several tiles and `st` records no graph (the base is a launch argument: a replay would see a spent
+  // counter and write nothing).
+  int begin(hipStream_t st, Pass *a, Pass *b = nullptr)
+  {
+    auto fits = [](const Pass *q) { return q && q->on && q->tiles >= 4 * (int64_t) q->grid; };
+    const bool dyn = d && dev_switch_int("FFT_DYN", 1) != 0 && (fits(a) || fits(b)) && !stream_is_capturing(st);
+    used = false;
+    for (Pass *q : {a, b})
+      if (q && (q->ctr = dyn && fits(q) ? d : nullptr)) used = true;
+    if (used && stale) {
+      TSD_HIP(hipMemsetAsync(d, 0, 256, st));
+      base = 0;
+      stale = false;
+    }
+    next = base;
+    for (Pass *q : {a, b})
+      if (q && q->ctr) {
+        q->base = next;
+        next += (unsigned) q->tiles + (unsigned) q->grid;
+      }
+    return TSDGPU_OK;
+  }
+  // The verdict on the step's launches: accepted, and the base moves past them; refused, and the device counter and the host
+  // base may have parted.
+  int commit()
+  {
+    if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
+      if (used) stale = true;
+      return set_err(TSDGPU_ERR_HIP, "fft_step: launch failed: %s", hipGetErrorString(le));
+    }
+    base = next;
+    return TSDGPU_OK;
+  }
+};
+
+}  // namespace
+
 struct tsdgpu_fft {
   int n = 0;
-  enum Kind { ONE, POW2_LDS, POW2_S16, POW2_W1024, POW2_W1M, POW2_4STEP, SMOOTH, ODDPOW2, MIXED, EVEN, ODD } kind = ONE;
+  enum Kind { ONE, POW2_LDS, POW2_S16, POW2_W1M, POW2_4STEP, SMOOTH, ODDPOW2, MIXED, EVEN, ODD } kind = ONE;
   // pow2
   int logn = 0;
   cpx *d_tw = nullptr;        // W_n^k, k < n/2 (LDS path) ...
@@ -1908,7 +1950,7 @@ struct tsdgpu_fft {
   cpx *d_tw1 = nullptr, *d_tw2 = nullptr, *d_thi = nullptr, *d_tlo = nullptr;
   // in-wave 1024-point FFT paths: lane twiddles (2 x 1024) and, for n = 2^20, TA [1024][64] / TD [1024][16]
   cpx *d_w1 = nullptr, *d_w2 = nullptr, *d_ta = nullptr, *d_td = nullptr, *d_w2k = nullptr;
-  unsigned *d_ctr = nullptr;  // n = 2^20: work counter of the dynamic tile hand-out (fft1m_cols_kernel), never reset
+  TileCounter ctr;            // the dynamic tile hand-out of the plans on fft1m_cols_kernel / fft2k_cols_kernel
   bool cols2k = false;        // four-step plan whose pass 2 (2048-point columns, N2 = 2048) runs on fft2k_cols_kernel
   bool cols2k_p1 = false;     // ... whose pass 1 (N1 = 2048) does
   bool p1k1 = false;          // n = 2^15 .. 2^19 ALSO planned as 1024 x C (calls of 2^21 points and more): pass 1 on fft1m_cols_kernel<1>
@@ -1917,8 +1959,6 @@ struct tsdgpu_fft {
   cpx *d_tw2a = nullptr;
   int c3 = 0;                 // three-pass plan n = 1024 x c3 x 1024 (c3 = 8, 16, 32; 0: not this plan); d_tp: W_C^(b p) [1024][c3]
   cpx *d_tp = nullptr;
-  unsigned ctr_base = 0;      // its value before the next launch (advanced once a launch pair has been accepted)
-  bool ctr_stale = false;     // a launch that used the counter failed: zero it again before the next use
   // even / odd
   tsdgpu_fft *sub = nullptr;
   cpx *d_rot = nullptr;       // W_n^k, k < n (even split)
@@ -1932,12 +1972,40 @@ struct tsdgpu_fft {
   cpx *d_twf = nullptr;       // n2 <= 1024: W_n2^(q i) in rows [i][17], i < n2 / 16 (fft_blu_wave_kernel)
   DevBuf work, work2, in_stage, out_stage;
   StepOrder order;            // top-level plans only (sub-plans run under their owner's)
-  // grouped schedule of the 2^20 plan (TSDGPU_FFT_GROUP): two side streams and their events
+};
+
+/* ---- real FFT ---------------------------------------------------------------------------- */
+struct tsdgpu_rfft {
+  int n = 0;
+  tsdgpu_fft *sub = nullptr;      // n/2-point complex plan (even n) or n-point plan (odd n)
+  cpx *d_rot = nullptr;           // tfr_rotation(n): W_n^i, double recurrence rounded to float
+  DevBuf work, in_stage, out_stage;
+  StepOrder order;
 };
 
 namespace {
 
 int log2_exact(int n) { int l = 0; while ((1 << l) < n) l++; return l; }
+
+// fn(int_c<V>()) for every V, in order
+template <int... Vs, typename FN> void for_each_int(FN fn) { (fn(int_c<Vs>()), ...); }
+
+// The kernels may take up to `BYTES` of dynamic LDS.  A refusal is dropped by the (void) hipGetLastError() that closes each
+// plan's list, and surfaces at the launch.
+template <int BYTES = 160 * 1024, typename... K> void raise_lds(K... kernels)
+{
+  ((void) hipFuncSetAttribute((const void *) kernels, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES), ...);
+}
+
+int cu_count()
+{
+  static const int NCU = [] {
+    int dev = 0, c = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+    return c > 0 ? c : 256;
+  }();
+  return NCU;
+}
 
 int upload(cpx **dst, const std::vector<cpx> &v)
 {
@@ -1958,6 +2026,54 @@ std::vector<cpx> twiddle_table(int n, int count)   // exp(-2 pi i k / n), k < co
   }
   if (count == 0) t[0] = make_float2(1.f, 0.f);
   return t;
+}
+
+// W_n^m, 0 <= m < n (the callers reduce the exponent): the angle in double, rounded once to float
+cpx root_of_unity(int64_t m, int64_t n)
+{
+  const double PI = 3.14159265358979323846;
+  const double a = -2.0 * PI * (double) m / (double) n;
+  return make_float2((float) std::cos(a), (float) std::sin(a));
+}
+
+// tfr_rotation_rapide (fourier.cc:32-46): W_n^i, i < n, by the double-precision recurrence r *= w0, rounded to float
+std::vector<cpx> rotation_table(int n)
+{
+  std::vector<cpx> rot((size_t) n);
+  const double PI = 3.14159265358979323846;
+  double rr = 1.0, ri = 0.0;
+  const double wr = std::cos(-2 * PI / n), wi = std::sin(-2 * PI / n);
+  for (int i = 0; i < n; i++) {
+    rot[i] = make_float2((float) rr, (float) ri);
+    const double tr = rr * wr - ri * wi, ti = rr * wi + ri * wr;
+    rr = tr; ri = ti;
+  }
+  return rot;
+}
+
+// the lane twiddles of the in-wave 1024-point FFT (fft1024_wave.hpp)
+int upload_w1024(tsdgpu_fft *p)
+{
+  std::vector<cpx> t1(1024), t2(1024);
+  w1024::fill_twiddles(t1.data(), t2.data());
+  if (const int rc = upload(&p->d_w1, t1)) return rc;
+  return upload(&p->d_w2, t2);
+}
+
+// The four-step twiddle W_n^(c k) of column c < C as the in-wave column kernels take it, k = k0(lane) + kd(r):
+// TA[c][lane] = W_n^(c k0), k0 = (lane >> 2) + 16 (lane & 3), and TD[c][r] = W_n^(c kd), kd = 64 (r >> 2) + 256 (r & 3), in rows
+// of `pitch` = 16, or 17 with W_n^(1024 c) in column 16 (the 2048-point columns of fft2k_cols_kernel<1>)
+int upload_lane_tables(tsdgpu_fft *p, int n, int C, int pitch)
+{
+  std::vector<cpx> ta((size_t) C * 64), td((size_t) C * pitch);
+  auto Wn = [n](int64_t m) { return root_of_unity(m & (n - 1), n); };      // (n is a power of two: m mod n without the division)
+  for (int c = 0; c < C; c++) {
+    for (int lane = 0; lane < 64; lane++) ta[(size_t) c * 64 + lane] = Wn((int64_t) c * ((lane >> 2) + 16 * (lane & 3)));
+    for (int r = 0; r < 16; r++) td[(size_t) c * pitch + r] = Wn((int64_t) c * (64 * (r >> 2) + 256 * (r & 3)));
+    if (pitch == 17) td[(size_t) c * pitch + 16] = Wn((int64_t) c * 1024);
+  }
+  if (const int rc = upload(&p->d_ta, ta)) return rc;
+  return upload(&p->d_td, td);
 }
 
 // prochaine_puissance_de_2 (libtsd core/src/tsd.cc:287-291), float-log based like the reference
@@ -1981,9 +2097,6 @@ bool mixed_split(int n, int *m, int *P)
   return true;
 }
 
-// n = 2^a 3^b 5^c 7^d 11^e 13^f, not a power of two, <= 16384: the one-kernel mixed-radix plan.
-// Radix sequence: 16s and the remaining 8 / 4 / 2, then the odd primes.  Threads per transform:
-// enough for every pass to keep its butterflies' inputs in MR_PTS registers.
 // n = m * P with m odd in 3 .. 15, P a power of two >= 16, m P / 16 <= 1024 threads and m LDS images within the CU: fft_oddpow2_kernel
 bool oddpow2_split(int n, int *m, int *P)
 {
@@ -2002,6 +2115,10 @@ bool oddpow2_split(int n, int *m, int *P)
   *P = pw;
   return true;
 }
+
+// n = 2^a 3^b 5^c 7^d 11^e 13^f, not a power of two, <= 16384: the one-kernel mixed-radix plan.
+// Radix sequence: 16s and the remaining 8 / 4 / 2, then the odd primes.  Threads per transform:
+// enough for every pass to keep its butterflies' inputs in MR_PTS registers.
 bool smooth_plan(int n, MrFactors *F, int *tpt_out)
 {
   if (n < 3 || n > 16384 || (n & (n - 1)) == 0) return false;
@@ -2041,316 +2158,242 @@ bool smooth_plan(int n, MrFactors *F, int *tpt_out)
   return true;
 }
 
+// ---- the plans, one function per kind: the tables, then the kernels that may take their LDS --------------------------------
+
+// n = 2^20 as 1024 x 1024 on fft1m_cols_kernel
+int init_pow2_w1m(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::POW2_W1M;
+  if (const int rc = upload_w1024(p)) return rc;
+  if (const int rc = upload_lane_tables(p, p->n, 1024, 16)) return rc;
+  p->ctr.alloc();
+  raise_lds(fft1m_cols_kernel<1, false>, fft1m_cols_kernel<2, false>, fft1m_cols_kernel<1, true>, fft1m_cols_kernel<2, true>);
+  (void) hipGetLastError();
+  return TSDGPU_OK;
+}
+
+// n = 16 .. 16384 on the radix-16 Stockham kernels
+int init_pow2_s16(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::POW2_S16;
+  const int rc = upload(&p->d_tw, twiddle_table(p->n, p->n / 16));       // W_n^i, i < n/16: the base twiddles of every pass
+  for_each_int<16, 8, 4, 2>([](auto r) { raise_lds(fft_s16_kernel<decltype(r)::value>); });
+  for_each_int<16, 8, 4, 2>([](auto r) { raise_lds(fft_s16_persistent_kernel<decltype(r)::value>); });
+  (void) hipGetLastError();
+  return rc;
+}
+
+// n <= 4096 on the radix-2 kernel (n < 16, or TSDGPU_FFT_GENERIC)
+int init_pow2_lds(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::POW2_LDS;
+  return upload(&p->d_tw, twiddle_table(p->n, p->n / 2));
+}
+
+// n = N1 x N2 in two column passes, with the plans that take a pass (or both, or add a third) onto the in-wave column kernels
+int init_pow2_4step(tsdgpu_fft *p, bool fast)
+{
+  const int n = p->n;
+  int rc = TSDGPU_OK;
+  TSD_CHECK(p->logn <= 28, "fft: n = %d exceeds the four-step limit 2^28 (two passes of at most 16384-point columns)", n);
+  p->kind = tsdgpu_fft::POW2_4STEP;
+  p->logN1 = p->logn / 2;
+  // n = 2^15 .. 2^19: planned a second time as 1024 x C, so that pass 1 of LARGE calls runs on the 2^20 plan's column kernel
+  // (in-wave 1024-point FFT, prefetched tiles, dynamic hand-out: 0.73 ms per 2^28 points against 0.88 for a fft_cols16_kernel
+  // pass); small calls keep the square split (a 128-KiB tile per workgroup costs a single 2^16-point transform 4 us of its 18);
+  // TSDGPU_FFT_NO_1K_P1=1: the square split always
+  const bool use1k = fast && p->logn >= 15 && p->logn <= 19 && dev_switch("FFT_NO_1K_P1") == nullptr;
+  p->logN2 = p->logn - p->logN1;
+  p->N1 = 1 << p->logN1;
+  p->N2 = 1 << p->logN2;
+  if ((rc = upload(&p->d_tw1, twiddle_table(p->N1, p->N1 / 2)))) return rc;
+  if ((rc = upload(&p->d_tw2, twiddle_table(p->N2, p->N2 / 2)))) return rc;
+  // W_n^m = thi[m >> 12] * tlo[m & 4095]
+  std::vector<cpx> hi((size_t) (n >> 12));
+  for (int a = 0; a < (n >> 12); a++) hi[a] = root_of_unity((int64_t) a * 4096, n);
+  if ((rc = upload(&p->d_thi, hi))) return rc;
+  if ((rc = upload(&p->d_tlo, twiddle_table(n, 4096)))) return rc;
+  if (use1k) {
+    p->logN2a = p->logn - 10;
+    p->N2a = 1 << p->logN2a;
+    if ((rc = upload(&p->d_tw2a, twiddle_table(p->N2a, p->N2a / 2)))) return rc;
+    if ((rc = upload_w1024(p))) return rc;
+    if ((rc = upload_lane_tables(p, n, p->N2a, 16))) return rc;
+    p->ctr.alloc();
+    raise_lds(fft1m_cols_kernel<1, false>, fft1m_cols_kernel<1, true>);
+    p->p1k1 = true;
+  }
+  // 2^24, 2^25: the three-pass plan; 2^23 keeps the 2048 x 4096 plan unless TSDGPU_FFT_3PASS_23=1 (measured: see DESIGN.md 3.3)
+  const bool use3 = p->logn >= 23 && p->logn <= 25 && dev_switch("FFT_NO_3PASS") == nullptr &&
+                    (p->logn > 23 || dev_switch_int("FFT_3PASS_23", 0) != 0);
+  if (!use3 && (p->N2 == 2048 || p->N1 == 2048) && (p->N1 & 15) == 0 && dev_switch("FFT_NO_2K") == nullptr) {
+    // 2048-point column passes on fft2k_cols_kernel: the in-wave engine's tables, W_2048^k0 (64 entries), the 16 constants
+    // W_2048^(64 a + 256 b) and, for the decimation-in-frequency form, W_2048^(64 i), i < 16
+    std::vector<cpx> w2k(96);
+    for (int i = 0; i < 96; i++)
+      w2k[i] = root_of_unity(i < 64 ? i : (i < 80 ? 64 * ((i - 64) >> 2) + 256 * ((i - 64) & 3) : 64 * (i - 80)), 2048);
+    if ((rc = upload_w1024(p))) return rc;
+    if ((rc = upload(&p->d_w2k, w2k))) return rc;
+    if (p->N1 == 1024) {
+      // pass 1 on fft1m_cols_kernel<1>: 1024-point columns of the N2 = 2048 columns
+      if ((rc = upload_lane_tables(p, n, p->N2, 16))) return rc;
+      raise_lds(fft1m_cols_kernel<1, false>, fft1m_cols_kernel<1, true>);
+    } else if (p->N1 == 2048) {
+      // pass 1 on fft2k_cols_kernel<1>
+      if ((rc = upload_lane_tables(p, n, p->N2, 17))) return rc;
+      p->cols2k_p1 = true;
+    }
+    p->ctr.alloc();
+    raise_lds(fft2k_cols_kernel<1, false>, fft2k_cols_kernel<1, true>, fft2k_cols_kernel<2, false>, fft2k_cols_kernel<2, true>);
+    p->cols2k = p->N2 == 2048;
+  }
+  if (use3) {
+    // three passes of 128-B row segments (fft_planes_kernel): n = 1024 x C1 x 1024
+    const int C1 = 1 << (p->logn - 20), C = C1 * 1024;
+    if ((rc = upload_w1024(p))) return rc;
+    if ((rc = upload_lane_tables(p, n, C, 16))) return rc;
+    std::vector<cpx> tp((size_t) 1024 * C1);
+    for (int b = 0; b < 1024; b++)
+      for (int q = 0; q < C1; q++) tp[(size_t) b * C1 + q] = root_of_unity((int64_t) b * q % C, C);
+    if ((rc = upload(&p->d_tp, tp))) return rc;
+    p->ctr.alloc();
+    raise_lds(fft1m_cols_kernel<1, false>, fft1m_cols_kernel<2, false>, fft1m_cols_kernel<1, true>, fft1m_cols_kernel<2, true>);
+    p->c3 = C1;
+  }
+  // the column tiles use up to ~150 KiB of the CU's 160 KiB LDS
+  for_each_int<16, 8, 4, 2>([](auto r) { raise_lds(fft_cols16_kernel<1, decltype(r)::value>, fft_cols16_kernel<2, decltype(r)::value>); });
+  raise_lds(fft_cols_kernel<true>, fft_cols_kernel<false>);
+  (void) hipGetLastError();
+  return TSDGPU_OK;
+}
+
+// n = m x P, m = 3 .. 15, in one kernel
+int init_oddpow2(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::ODDPOW2;
+  const int n = p->n, m = p->mix_m, P = p->mix_P;
+  p->logn = log2_exact(P);
+  if (const int rc = upload(&p->d_wm, twiddle_table(m, m))) return rc;             // W_m^j
+  if (const int rc = upload(&p->d_rot, twiddle_table(n, n))) return rc;            // W_n^j
+  if (const int rc = upload(&p->d_tw, twiddle_table(P, std::max(1, P / 16)))) return rc;
+  for_each_int<16, 8, 4, 2>([](auto r) {
+    constexpr int R = decltype(r)::value;
+    raise_lds(fft_oddpow2_kernel<R, 4>, fft_oddpow2_kernel<R, 8>, fft_oddpow2_kernel<R, 16>);
+  });
+  (void) hipGetLastError();
+  return TSDGPU_OK;
+}
+
+// n = 2^a 3^b 5^c 7^d 11^e 13^f in one kernel
+int init_smooth(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::SMOOTH;
+  if (const int rc = upload(&p->d_rot, twiddle_table(p->n, p->n))) return rc;      // W_n^j
+  raise_lds(fft_mr_kernel);
+  (void) hipGetLastError();
+  return TSDGPU_OK;
+}
+
+// n = m x P, m odd up to 8191: m-point transforms (direct, or Bluestein), then P-point columns
+int init_mixed(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::MIXED;
+  const int n = p->n, m = p->mix_m, P = p->mix_P;
+  p->logn = log2_exact(P);
+  if (m <= 31) {
+    if (const int rc = upload(&p->d_wm, twiddle_table(m, m))) return rc;           // pass 1 = direct m-point DFT
+  } else {
+    if (const int rc = plan_create(&p->sub, m)) return rc;                           // pass 1 = one-kernel Bluestein
+    TSD_CHECK(p->sub->kind == tsdgpu_fft::ODD && p->sub->blu_fused, "fft: no fused Bluestein plan for m = %d", m);
+  }
+  if (const int rc = upload(&p->d_rot, twiddle_table(n, n))) return rc;            // W_n^j: the four-step twiddles
+  if (const int rc = upload(&p->d_tw, twiddle_table(P, std::max(1, P / 16)))) return rc;
+  for_each_int<16, 8, 4, 2>([](auto r) { raise_lds(fft_cols16_kernel<2, decltype(r)::value>); });
+  raise_lds<96 * 1024>(fft_odd_dft_kernel<8>, fft_odd_dft_kernel<16>, fft_odd_dft_kernel<32>);
+  (void) hipGetLastError();
+  return TSDGPU_OK;
+}
+
+// even n with a large odd part: the even / odd split over an n/2-point plan
+int init_even(tsdgpu_fft *p)
+{
+  p->kind = tsdgpu_fft::EVEN;
+  if (const int rc = plan_create(&p->sub, p->n / 2)) return rc;
+  return upload(&p->d_rot, rotation_table(p->n));
+}
+
+// odd n: Bluestein over n2 = the next power of two from 2n - 1, in one kernel where that is a Stockham size
+int init_odd(tsdgpu_fft *p)
+{
+  const int n = p->n;
+  int rc = TSDGPU_OK;
+  p->kind = tsdgpu_fft::ODD;
+  p->n2 = ref_next_pow2(2 * n - 1);
+  if ((rc = plan_create(&p->sub, p->n2))) return rc;
+  // chirp = polar(square(linspace(-(n-1), n-1, 2n-1)) / 2 * (-2 pi / n)), all in float like
+  // the reference (fourier.cc:396-399): the float rounding of the angle is part of its result
+  std::vector<cpx> chirp((size_t) (2 * n - 1)), icp((size_t) p->n2, make_float2(0.f, 0.f));
+  const double step = ((double) (float) (n - 1) - (double) (float) -(n - 1)) / (2 * n - 2);
+  const float mul = (float) (-2 * 3.14159265358979323846 / n);
+  for (int i = 0; i < 2 * n - 1; i++) {
+    const float t = i == 0 ? (float) -(n - 1) : (float) ((double) (float) -(n - 1) + step * i);
+    float v = (t * t) / 2;
+    v *= mul;
+    chirp[i] = make_float2(std::cos(v), std::sin(v));
+    icp[i] = make_float2(chirp[i].x, -chirp[i].y);
+  }
+  if ((rc = upload(&p->d_chirp, chirp))) return rc;
+  cpx *d_icp = nullptr;
+  if ((rc = upload(&d_icp, icp))) return rc;
+  if (hipMalloc((void **) &p->d_xc, (size_t) p->n2 * sizeof(cpx)) != hipSuccess) {
+    (void) hipFree(d_icp);
+    return set_err(TSDGPU_ERR_HIP, "fft: hipMalloc failed");
+  }
+  rc = tsdgpu_fft_step(p->sub, d_icp, p->d_xc, 1, 1, nullptr);
+  (void) hipDeviceSynchronize();
+  (void) hipFree(d_icp);
+  if (!rc && p->n2 >= 16 && p->n2 <= S16_MAX_N && dev_switch("FFT_GENERIC") == nullptr) {
+    p->blu_fused = true;
+    rc = upload(&p->d_tw, twiddle_table(p->n2, p->n2 / 16));
+    if (!rc && p->n2 <= 1024) {
+      const int tp = p->n2 / 16;
+      std::vector<cpx> twf((size_t) tp * BW_TWROW, make_float2(1.f, 0.f));
+      for (int i = 0; i < tp; i++)
+        for (int q = 0; q < 16; q++) twf[(size_t) i * BW_TWROW + q] = root_of_unity((q * i) % p->n2, p->n2);
+      rc = upload(&p->d_twf, twf);
+    }
+    for_each_int<16, 8, 4, 2>([](auto r) { raise_lds(fft_bluestein_kernel<decltype(r)::value>); });
+    for_each_int<1, 2, 4, 8, 16, 32, 64, 128>([](auto t) {
+      raise_lds(fft_blu_wave_kernel<decltype(t)::value, false>, fft_blu_wave_kernel<decltype(t)::value, true>);
+    });
+    (void) hipGetLastError();
+  }
+  return rc;
+}
+
+// The kinds in the order they are tried; a switch is read where its kind is reached.
 int plan_init(tsdgpu_fft *p, int n)
 {
   p->n = n;
-  int rc = TSDGPU_OK;
   if (n == 1) {
     p->kind = tsdgpu_fft::ONE;
-  } else if ((n & (n - 1)) == 0) {
+    return TSDGPU_OK;
+  }
+  if ((n & (n - 1)) == 0) {
     p->logn = log2_exact(n);
     const bool fast = dev_switch("FFT_GENERIC") == nullptr;
-    if (fast && n == (1 << 20)) {
-      p->kind = n == 1024 ? tsdgpu_fft::POW2_W1024 : tsdgpu_fft::POW2_W1M;
-      std::vector<cpx> t1(1024), t2(1024);
-      w1024::fill_twiddles(t1.data(), t2.data());
-      if ((rc = upload(&p->d_w1, t1))) return rc;
-      if ((rc = upload(&p->d_w2, t2))) return rc;
-      if (n != 1024) {
-        std::vector<cpx> ta((size_t) 1024 * 64), td((size_t) 1024 * 16);
-        const double PI = 3.14159265358979323846;
-        for (int c = 0; c < 1024; c++) {
-          for (int lane = 0; lane < 64; lane++) {
-            const int64_t m = ((int64_t) c * ((lane >> 2) + 16 * (lane & 3))) % n;
-            const double a = -2.0 * PI * (double) m / (double) n;
-            ta[(size_t) c * 64 + lane] = make_float2((float) std::cos(a), (float) std::sin(a));
-          }
-          for (int r = 0; r < 16; r++) {
-            const int64_t m = ((int64_t) c * (64 * (r >> 2) + 256 * (r & 3))) % n;
-            const double a = -2.0 * PI * (double) m / (double) n;
-            td[(size_t) c * 16 + r] = make_float2((float) std::cos(a), (float) std::sin(a));
-          }
-        }
-        if ((rc = upload(&p->d_ta, ta))) return rc;
-        if ((rc = upload(&p->d_td, td))) return rc;
-        if (hipMalloc((void **) &p->d_ctr, 256) != hipSuccess || hipMemset(p->d_ctr, 0, 256) != hipSuccess) {
-          (void) hipGetLastError();
-          p->d_ctr = nullptr;                                // (the static partition then)
-        }
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipGetLastError();
-      }
-    } else if (fast && n >= 16 && n <= S16_MAX_N) {
-      p->kind = tsdgpu_fft::POW2_S16;
-      rc = upload(&p->d_tw, twiddle_table(n, n / 16));       // W_n^i, i < n/16: the base twiddles of every pass
-#define S16_ATTR(R) (void) hipFuncSetAttribute((const void *) fft_s16_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      S16_ATTR(16); S16_ATTR(8); S16_ATTR(4); S16_ATTR(2);
-#undef S16_ATTR
-#define S16P_ATTR(R) (void) hipFuncSetAttribute((const void *) fft_s16_persistent_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      S16P_ATTR(16); S16P_ATTR(8); S16P_ATTR(4); S16P_ATTR(2);
-#undef S16P_ATTR
-      (void) hipGetLastError();
-    } else if (n <= LDS_MAX_N) {
-      p->kind = tsdgpu_fft::POW2_LDS;
-      rc = upload(&p->d_tw, twiddle_table(n, n / 2));
-    } else {
-      TSD_CHECK(p->logn <= 28, "fft: n = %d exceeds the four-step limit 2^28 (two passes of at most 16384-point columns)", n);
-      p->kind = tsdgpu_fft::POW2_4STEP;
-      p->logN1 = p->logn / 2;
-      // n = 2^15 .. 2^19: planned a second time as 1024 x C, so that pass 1 of LARGE calls runs on the 2^20 plan's column kernel
-      // (in-wave 1024-point FFT, prefetched tiles, dynamic hand-out: 0.73 ms per 2^28 points against 0.88 for a fft_cols16_kernel
-      // pass); small calls keep the square split (a 128-KiB tile per workgroup costs a single 2^16-point transform 4 us of its 18);
-      // TSDGPU_FFT_NO_1K_P1=1: the square split always
-      const bool use1k = fast && p->logn >= 15 && p->logn <= 19 && dev_switch("FFT_NO_1K_P1") == nullptr;
-      p->logN2 = p->logn - p->logN1;
-      p->N1 = 1 << p->logN1;
-      p->N2 = 1 << p->logN2;
-      if ((rc = upload(&p->d_tw1, twiddle_table(p->N1, p->N1 / 2)))) return rc;
-      if ((rc = upload(&p->d_tw2, twiddle_table(p->N2, p->N2 / 2)))) return rc;
-      // W_n^m = thi[m >> 12] * tlo[m & 4095]
-      std::vector<cpx> hi((size_t) (n >> 12)), lo(4096);
-      const double PI = 3.14159265358979323846;
-      for (int a = 0; a < (n >> 12); a++) {
-        const double ang = -2.0 * PI * ((double) a * 4096.0) / (double) n;
-        hi[a] = make_float2((float) std::cos(ang), (float) std::sin(ang));
-      }
-      for (int b = 0; b < 4096; b++) {
-        const double ang = -2.0 * PI * (double) b / (double) n;
-        lo[b] = make_float2((float) std::cos(ang), (float) std::sin(ang));
-      }
-      if ((rc = upload(&p->d_thi, hi))) return rc;
-      if ((rc = upload(&p->d_tlo, lo))) return rc;
-      if (use1k) {
-        p->logN2a = p->logn - 10;
-        p->N2a = 1 << p->logN2a;
-        if ((rc = upload(&p->d_tw2a, twiddle_table(p->N2a, p->N2a / 2)))) return rc;
-        std::vector<cpx> t1(1024), t2(1024);
-        w1024::fill_twiddles(t1.data(), t2.data());
-        if ((rc = upload(&p->d_w1, t1))) return rc;
-        if ((rc = upload(&p->d_w2, t2))) return rc;
-        std::vector<cpx> ta((size_t) p->N2a * 64), td((size_t) p->N2a * 16);
-        for (int c = 0; c < p->N2a; c++) {
-          for (int lane = 0; lane < 64; lane++) {
-            const double a = -2.0 * PI * (double) (((int64_t) c * ((lane >> 2) + 16 * (lane & 3))) % n) / (double) n;
-            ta[(size_t) c * 64 + lane] = make_float2((float) std::cos(a), (float) std::sin(a));
-          }
-          for (int r = 0; r < 16; r++) {
-            const double a = -2.0 * PI * (double) (((int64_t) c * (64 * (r >> 2) + 256 * (r & 3))) % n) / (double) n;
-            td[(size_t) c * 16 + r] = make_float2((float) std::cos(a), (float) std::sin(a));
-          }
-        }
-        if ((rc = upload(&p->d_ta, ta))) return rc;
-        if ((rc = upload(&p->d_td, td))) return rc;
-        if (hipMalloc((void **) &p->d_ctr, 256) != hipSuccess || hipMemset(p->d_ctr, 0, 256) != hipSuccess) {
-          (void) hipGetLastError();
-          p->d_ctr = nullptr;
-        }
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        p->p1k1 = true;
-      }
-      // 2^24, 2^25: the three-pass plan; 2^23 keeps the 2048 x 4096 plan unless TSDGPU_FFT_3PASS_23=1 (measured: see DESIGN.md 3.3)
-      const bool use3 = p->logn >= 23 && p->logn <= 25 && dev_switch("FFT_NO_3PASS") == nullptr &&
-                        (p->logn > 23 || dev_switch_int("FFT_3PASS_23", 0) != 0);
-      if (!use3 && (p->N2 == 2048 || p->N1 == 2048) && (p->N1 & 15) == 0 && dev_switch("FFT_NO_2K") == nullptr) {
-        // 2048-point column passes on fft2k_cols_kernel: the in-wave engine's tables, W_2048^k0 (64 entries) and the 16 constants
-        // W_2048^(64 a + 256 b)
-        std::vector<cpx> t1(1024), t2(1024), w2k(96);       // (... and, for the decimation-in-frequency form, W_2048^(64 i), i < 16)
-        w1024::fill_twiddles(t1.data(), t2.data());
-        for (int i = 0; i < 96; i++) {
-          const int m = i < 64 ? i : (i < 80 ? 64 * ((i - 64) >> 2) + 256 * ((i - 64) & 3) : 64 * (i - 80));
-          const double ang = -2.0 * PI * (double) m / 2048.0;
-          w2k[i] = make_float2((float) std::cos(ang), (float) std::sin(ang));
-        }
-        if ((rc = upload(&p->d_w1, t1))) return rc;
-        if ((rc = upload(&p->d_w2, t2))) return rc;
-        if ((rc = upload(&p->d_w2k, w2k))) return rc;
-        auto Wn = [&](int64_t m) {
-          const double a = -2.0 * PI * (double) (m % n) / (double) n;
-          return make_float2((float) std::cos(a), (float) std::sin(a));
-        };
-        if (p->N1 == 1024) {
-          // pass 1 on fft1m_cols_kernel<1>: 1024-point columns of the N2 = 2048 columns, four-step twiddle W_n^(c k) as TA[c][lane] TD[c][r]
-          std::vector<cpx> ta((size_t) p->N2 * 64), td((size_t) p->N2 * 16);
-          for (int c = 0; c < p->N2; c++) {
-            for (int lane = 0; lane < 64; lane++) ta[(size_t) c * 64 + lane] = Wn((int64_t) c * ((lane >> 2) + 16 * (lane & 3)));
-            for (int r = 0; r < 16; r++) td[(size_t) c * 16 + r] = Wn((int64_t) c * (64 * (r >> 2) + 256 * (r & 3)));
-          }
-          if ((rc = upload(&p->d_ta, ta))) return rc;
-          if ((rc = upload(&p->d_td, td))) return rc;
-          (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        } else if (p->N1 == 2048) {
-          // pass 1 on fft2k_cols_kernel<1>: TA[c][lane] = W_n^(c k0), TD[c][r] = W_n^(c (64 a + 256 b)), TD[c][16] = W_n^(1024 c)
-          std::vector<cpx> ta((size_t) p->N2 * 64), td((size_t) p->N2 * 17);
-          for (int c = 0; c < p->N2; c++) {
-            for (int lane = 0; lane < 64; lane++) ta[(size_t) c * 64 + lane] = Wn((int64_t) c * ((lane >> 2) + 16 * (lane & 3)));
-            for (int r = 0; r < 16; r++) td[(size_t) c * 17 + r] = Wn((int64_t) c * (64 * (r >> 2) + 256 * (r & 3)));
-            td[(size_t) c * 17 + 16] = Wn((int64_t) c * 1024);
-          }
-          if ((rc = upload(&p->d_ta, ta))) return rc;
-          if ((rc = upload(&p->d_td, td))) return rc;
-          p->cols2k_p1 = true;
-        }
-        if (hipMalloc((void **) &p->d_ctr, 256) != hipSuccess || hipMemset(p->d_ctr, 0, 256) != hipSuccess) {
-          (void) hipGetLastError();
-          p->d_ctr = nullptr;                                // (the static partition then)
-        }
-        (void) hipFuncSetAttribute((const void *) fft2k_cols_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft2k_cols_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft2k_cols_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft2k_cols_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        p->cols2k = p->N2 == 2048;
-      }
-      if (use3) {
-        // three passes of 128-B row segments (fft_planes_kernel): n = 1024 x C1 x 1024
-        const int C1 = 1 << (p->logn - 20), C = C1 * 1024;
-        std::vector<cpx> t1(1024), t2(1024);
-        w1024::fill_twiddles(t1.data(), t2.data());
-        if ((rc = upload(&p->d_w1, t1))) return rc;
-        if ((rc = upload(&p->d_w2, t2))) return rc;
-        auto Wd = [&](int64_t m, int64_t mod) {
-          const double a = -2.0 * PI * (double) (m % mod) / (double) mod;
-          return make_float2((float) std::cos(a), (float) std::sin(a));
-        };
-        {
-          std::vector<cpx> ta((size_t) C * 64), td((size_t) C * 16), tp((size_t) 1024 * C1);
-          for (int c = 0; c < C; c++) {
-            for (int lane = 0; lane < 64; lane++) ta[(size_t) c * 64 + lane] = Wd((int64_t) c * ((lane >> 2) + 16 * (lane & 3)), n);
-            for (int r = 0; r < 16; r++) td[(size_t) c * 16 + r] = Wd((int64_t) c * (64 * (r >> 2) + 256 * (r & 3)), n);
-          }
-          for (int b = 0; b < 1024; b++)
-            for (int q = 0; q < C1; q++) tp[(size_t) b * C1 + q] = Wd((int64_t) b * q, C);
-          if ((rc = upload(&p->d_ta, ta))) return rc;
-          if ((rc = upload(&p->d_td, td))) return rc;
-          if ((rc = upload(&p->d_tp, tp))) return rc;
-        }
-        if (hipMalloc((void **) &p->d_ctr, 256) != hipSuccess || hipMemset(p->d_ctr, 0, 256) != hipSuccess) {
-          (void) hipGetLastError();
-          p->d_ctr = nullptr;
-        }
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void) hipFuncSetAttribute((const void *) fft1m_cols_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        p->c3 = C1;
-      }
-      // the column tiles use up to ~150 KiB of the CU's 160 KiB LDS
-#define C16_ATTR(P, R) (void) hipFuncSetAttribute((const void *) fft_cols16_kernel<P, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      C16_ATTR(1, 16); C16_ATTR(1, 8); C16_ATTR(1, 4); C16_ATTR(1, 2); C16_ATTR(2, 16); C16_ATTR(2, 8); C16_ATTR(2, 4); C16_ATTR(2, 2);
-#undef C16_ATTR
-      (void) hipFuncSetAttribute((const void *) fft_cols_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipFuncSetAttribute((const void *) fft_cols_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipGetLastError();
-    }
-  } else if (oddpow2_split(n, &p->mix_m, &p->mix_P) && dev_switch("FFT_GENERIC") == nullptr && dev_switch("FFT_NO_SMOOTH") == nullptr &&
-             dev_switch("FFT_NO_ODDPOW2") == nullptr) {
-    p->kind = tsdgpu_fft::ODDPOW2;
-    const int m = p->mix_m, P = p->mix_P;
-    p->logn = log2_exact(P);
-    if ((rc = upload(&p->d_wm, twiddle_table(m, m)))) return rc;             // W_m^j
-    if ((rc = upload(&p->d_rot, twiddle_table(n, n)))) return rc;            // W_n^j
-    if ((rc = upload(&p->d_tw, twiddle_table(P, std::max(1, P / 16))))) return rc;
-#define OP_ATTR(R) (void) hipFuncSetAttribute((const void *) fft_oddpow2_kernel<R, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  (void) hipFuncSetAttribute((const void *) fft_oddpow2_kernel<R, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
-  (void) hipFuncSetAttribute((const void *) fft_oddpow2_kernel<R, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-    OP_ATTR(16); OP_ATTR(8); OP_ATTR(4); OP_ATTR(2);
-#undef OP_ATTR
-    (void) hipGetLastError();
-  } else if (smooth_plan(n, &p->mr, &p->mr_tpt) && dev_switch("FFT_GENERIC") == nullptr && dev_switch("FFT_NO_SMOOTH") == nullptr) {
-    p->kind = tsdgpu_fft::SMOOTH;
-    if ((rc = upload(&p->d_rot, twiddle_table(n, n)))) return rc;            // W_n^j
-    (void) hipFuncSetAttribute((const void *) fft_mr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void) hipGetLastError();
-  } else if ((n & 1) == 0 && mixed_split(n, &p->mix_m, &p->mix_P) && dev_switch("FFT_GENERIC") == nullptr) {
-    p->kind = tsdgpu_fft::MIXED;
-    const int m = p->mix_m, P = p->mix_P;
-    p->logn = log2_exact(P);
-    if (m <= 31) {
-      if ((rc = upload(&p->d_wm, twiddle_table(m, m)))) return rc;           // pass 1 = direct m-point DFT
-    } else {
-      if ((rc = plan_create(&p->sub, m))) return rc;                           // pass 1 = one-kernel Bluestein
-      TSD_CHECK(p->sub->kind == tsdgpu_fft::ODD && p->sub->blu_fused, "fft: no fused Bluestein plan for m = %d", m);
-    }
-    if ((rc = upload(&p->d_rot, twiddle_table(n, n)))) return rc;            // W_n^j: the four-step twiddles
-    if ((rc = upload(&p->d_tw, twiddle_table(P, std::max(1, P / 16))))) return rc;
-#define C16_ATTR(R) (void) hipFuncSetAttribute((const void *) fft_cols16_kernel<2, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-    C16_ATTR(16); C16_ATTR(8); C16_ATTR(4); C16_ATTR(2);
-#undef C16_ATTR
-    (void) hipFuncSetAttribute((const void *) fft_odd_dft_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void) hipFuncSetAttribute((const void *) fft_odd_dft_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void) hipFuncSetAttribute((const void *) fft_odd_dft_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void) hipGetLastError();
-  } else if ((n & 1) == 0) {
-    p->kind = tsdgpu_fft::EVEN;
-    if ((rc = plan_create(&p->sub, n / 2))) return rc;
-    // tfr_rotation_rapide (fourier.cc:32-46): double-precision recurrence r *= w0, rounded to float
-    std::vector<cpx> rot((size_t) n);
-    const double PI = 3.14159265358979323846;
-    double rr = 1.0, ri = 0.0;
-    const double wr = std::cos(-2 * PI / n), wi = std::sin(-2 * PI / n);
-    for (int i = 0; i < n; i++) {
-      rot[i] = make_float2((float) rr, (float) ri);
-      const double tr = rr * wr - ri * wi, ti = rr * wi + ri * wr;
-      rr = tr; ri = ti;
-    }
-    rc = upload(&p->d_rot, rot);
-  } else {
-    p->kind = tsdgpu_fft::ODD;
-    p->n2 = ref_next_pow2(2 * n - 1);
-    if ((rc = plan_create(&p->sub, p->n2))) return rc;
-    // chirp = polar(square(linspace(-(n-1), n-1, 2n-1)) / 2 * (-2 pi / n)), all in float like
-    // the reference (fourier.cc:396-399): the float rounding of the angle is part of its result
-    std::vector<cpx> chirp((size_t) (2 * n - 1)), icp((size_t) p->n2, make_float2(0.f, 0.f));
-    const double step = ((double) (float) (n - 1) - (double) (float) -(n - 1)) / (2 * n - 2);
-    const float mul = (float) (-2 * 3.14159265358979323846 / n);
-    for (int i = 0; i < 2 * n - 1; i++) {
-      const float t = i == 0 ? (float) -(n - 1) : (float) ((double) (float) -(n - 1) + step * i);
-      float v = (t * t) / 2;
-      v *= mul;
-      chirp[i] = make_float2(std::cos(v), std::sin(v));
-      icp[i] = make_float2(chirp[i].x, -chirp[i].y);
-    }
-    if ((rc = upload(&p->d_chirp, chirp))) return rc;
-    cpx *d_icp = nullptr;
-    if ((rc = upload(&d_icp, icp))) return rc;
-    if (hipMalloc((void **) &p->d_xc, (size_t) p->n2 * sizeof(cpx)) != hipSuccess) {
-      (void) hipFree(d_icp);
-      return set_err(TSDGPU_ERR_HIP, "fft: hipMalloc failed");
-    }
-    rc = tsdgpu_fft_step(p->sub, d_icp, p->d_xc, 1, 1, nullptr);
-    (void) hipDeviceSynchronize();
-    (void) hipFree(d_icp);
-    if (!rc && p->n2 >= 16 && p->n2 <= S16_MAX_N && dev_switch("FFT_GENERIC") == nullptr) {
-      p->blu_fused = true;
-      rc = upload(&p->d_tw, twiddle_table(p->n2, p->n2 / 16));
-      if (!rc && p->n2 <= 1024) {
-        const int tp = p->n2 / 16;
-        std::vector<cpx> twf((size_t) tp * BW_TWROW, make_float2(1.f, 0.f));
-        const double PI = 3.14159265358979323846;
-        for (int i = 0; i < tp; i++)
-          for (int q = 0; q < 16; q++) {
-            const double a = -2.0 * PI * (double) ((q * i) % p->n2) / (double) p->n2;
-            twf[(size_t) i * BW_TWROW + q] = make_float2((float) std::cos(a), (float) std::sin(a));
-          }
-        rc = upload(&p->d_twf, twf);
-      }
-      (void) hipFuncSetAttribute((const void *) fft_bluestein_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipFuncSetAttribute((const void *) fft_bluestein_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipFuncSetAttribute((const void *) fft_bluestein_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void) hipFuncSetAttribute((const void *) fft_bluestein_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#define BW_ATTR(R)                                                                                                                   \
-  (void) hipFuncSetAttribute((const void *) fft_blu_wave_kernel<R, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-  (void) hipFuncSetAttribute((const void *) fft_blu_wave_kernel<R, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-      BW_ATTR(1); BW_ATTR(2); BW_ATTR(4); BW_ATTR(8); BW_ATTR(16); BW_ATTR(32); BW_ATTR(64); BW_ATTR(128);
-#undef BW_ATTR
-      (void) hipGetLastError();
-    }
+    if (fast && n == (1 << 20)) return init_pow2_w1m(p);
+    if (fast && n >= 16 && n <= S16_MAX_N) return init_pow2_s16(p);
+    if (n <= LDS_MAX_N) return init_pow2_lds(p);
+    return init_pow2_4step(p, fast);
   }
-  return rc;
+  if (oddpow2_split(n, &p->mix_m, &p->mix_P) && dev_switch("FFT_GENERIC") == nullptr && dev_switch("FFT_NO_SMOOTH") == nullptr &&
+      dev_switch("FFT_NO_ODDPOW2") == nullptr)
+    return init_oddpow2(p);
+  if (smooth_plan(n, &p->mr, &p->mr_tpt) && dev_switch("FFT_GENERIC") == nullptr && dev_switch("FFT_NO_SMOOTH") == nullptr) return init_smooth(p);
+  if ((n & 1) == 0 && mixed_split(n, &p->mix_m, &p->mix_P) && dev_switch("FFT_GENERIC") == nullptr) return init_mixed(p);
+  if ((n & 1) == 0) return init_even(p);
+  return init_odd(p);
 }
 
 int plan_create(tsdgpu_fft **out, int n)
@@ -2369,7 +2412,7 @@ void plan_destroy(tsdgpu_fft *p)
 {
   if (!p) return;
   if (p->sub) plan_destroy(p->sub);
-  if (p->d_ctr) (void) hipFree(p->d_ctr);
+  p->ctr.release();
   for (cpx *q : {p->d_tw, p->d_tw1, p->d_tw2, p->d_thi, p->d_tlo, p->d_rot, p->d_chirp, p->d_xc, p->d_twf, p->d_tp, p->d_tw2a, p->d_w1, p->d_w2, p->d_ta, p->d_td, p->d_wm, p->d_w2k})
     if (q) (void) hipFree(q);
   p->work.release();
@@ -2391,15 +2434,6 @@ bool bluestein_fusable(const tsdgpu_fft *sub, int P)
   const int n2 = sub->n2, tpt = n2 / 16;
   return !off && sub->blu_fused && (P == 2 || P == 4 || P == 8 || P == 16) && P * tpt <= 1024 &&
          (size_t) std::max(256 / tpt, P) * (n2 + n2 / 16) * sizeof(cpx) <= 158 * 1024;
-}
-int cu_count()
-{
-  static const int NCU = [] {
-    int dev = 0, c = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return c > 0 ? c : 256;
-  }();
-  return NCU;
 }
 // the wave-level kernel serves transforms of at most 64 threads (n2 <= 1024); fused groups of P residues within 512 threads
 // (TSDGPU_FFT_BLU_OLD=1: fft_bluestein_kernel everywhere)
@@ -2442,31 +2476,20 @@ int launch_blu_wave(const tsdgpu_fft *p, const cpx *x, cpx *y, float *pw, const 
   };
   const BluArgs A{x, y, pw, p->d_chirp, p->d_xc, tab ? p->d_twf : p->d_tw, Wn, win, n, n2, tpt, reverse, logP, conj_out, fuse ? P : 0, gf,
                   1.0f / std::sqrt((float) P), ntr, bstride};
-#define BW_LAUNCH(TP)                                                                                                          \
-  do {                                                                                                                         \
-    const void *fn = pw_rows ? (const void *) fft_blu_wave_kernel<TP, true> : (const void *) fft_blu_wave_kernel<TP, false>;   \
-    const int64_t grid = std::min<int64_t>(nslots, (int64_t) cu_count() * resident(fn));                                        \
-    if (pw_rows) {                                                                                                             \
-      *pw_rows = grid;                                                                                                         \
-      if (!pw) return TSDGPU_OK;                                                                                               \
-      TSD_CHECK(*pw_rows <= pw_cap, "welch: %lld partial rows, room for %lld", (long long) *pw_rows, (long long) pw_cap);      \
-    }                                                                                                                          \
-    if (pw) hipLaunchKernelGGL((fft_blu_wave_kernel<TP, true>), dim3((unsigned) grid), dim3(NT), lds, st, A);                  \
-    else hipLaunchKernelGGL((fft_blu_wave_kernel<TP, false>), dim3((unsigned) grid), dim3(NT), lds, st, A);                    \
-  } while (0)
-  switch (tpt) {
-    case 1: BW_LAUNCH(1); break;
-    case 2: BW_LAUNCH(2); break;
-    case 4: BW_LAUNCH(4); break;
-    case 8: BW_LAUNCH(8); break;
-    case 16: BW_LAUNCH(16); break;
-    case 32: BW_LAUNCH(32); break;
-    case 64: BW_LAUNCH(64); break;
-    default: BW_LAUNCH(128); break;
-  }
-#undef BW_LAUNCH
-  TSD_HIP(hipGetLastError());
-  return TSDGPU_OK;
+  return int_switch<1, 2, 4, 8, 16, 32, 64, 128>(tpt, [&](auto tp) -> int {
+    constexpr int TP = decltype(tp)::value;
+    const void *fn = pw_rows ? (const void *) fft_blu_wave_kernel<TP, true> : (const void *) fft_blu_wave_kernel<TP, false>;
+    const int64_t grid = std::min<int64_t>(nslots, (int64_t) cu_count() * resident(fn));
+    if (pw_rows) {
+      *pw_rows = grid;
+      if (!pw) return TSDGPU_OK;
+      TSD_CHECK(*pw_rows <= pw_cap, "welch: %lld partial rows, room for %lld", (long long) *pw_rows, (long long) pw_cap);
+    }
+    if (pw) hipLaunchKernelGGL((fft_blu_wave_kernel<TP, true>), dim3((unsigned) grid), dim3(NT), lds, st, A);
+    else hipLaunchKernelGGL((fft_blu_wave_kernel<TP, false>), dim3((unsigned) grid), dim3(NT), lds, st, A);
+    TSD_HIP(hipGetLastError());
+    return TSDGPU_OK;
+  });
 }
 int launch_bluestein(const tsdgpu_fft *p, const cpx *x, cpx *y, int64_t ntr, int reverse, int conj_out, int P, const cpx *Wn,
                      hipStream_t st, bool fuse = false)
@@ -2475,9 +2498,7 @@ int launch_bluestein(const tsdgpu_fft *p, const cpx *x, cpx *y, int64_t ntr, int
   // unitary FFT, product with the unitary xc, unitary inverse, times sqrt(n2)/sqrt(n): the two
   // unnormalised transforms carry n2, so the output factor is sqrt(n2)/sqrt(n) / n2
   const float gf = std::sqrt((float) n2) / std::sqrt((float) n) / (float) n2;
-  int l2 = 0;
-  while ((1 << l2) < n2) l2++;
-  const int r0 = 1 << ((l2 & 3) == 0 ? 4 : (l2 & 3)), tpt = n2 / 16;
+  const int tpt = n2 / 16;
   if (blu_wave_fits(p, P, fuse))
     return launch_blu_wave(p, x, y, nullptr, nullptr, (int64_t) n * P, ntr, reverse, conj_out, P, Wn, st, fuse);
   const int threads = std::max(256, fuse ? P * tpt : tpt), T = threads / tpt;       // (fused: whole groups of P residues per workgroup)
@@ -2485,19 +2506,336 @@ int launch_bluestein(const tsdgpu_fft *p, const cpx *x, cpx *y, int64_t ntr, int
   const int64_t grid = cdiv(ntr, T);
   TSD_CHECK(grid <= 0x7fffffff, "fft_step: too many transforms");
   const float s2 = 1.0f / std::sqrt((float) P);
-#define BLU_LAUNCH(R) hipLaunchKernelGGL((fft_bluestein_kernel<R>), dim3((unsigned) grid), dim3(threads), lds, st, x, y, p->d_chirp, p->d_xc, p->d_tw, n, n2, tpt, reverse, gf, P, Wn, conj_out, ntr, fuse ? P : 0, s2)
-  if (r0 == 16) BLU_LAUNCH(16); else if (r0 == 8) BLU_LAUNCH(8); else if (r0 == 4) BLU_LAUNCH(4); else BLU_LAUNCH(2);
-#undef BLU_LAUNCH
+  s16_radix(first_radix(log2_exact(n2)), [&](auto r) {
+    hipLaunchKernelGGL((fft_bluestein_kernel<decltype(r)::value>), dim3((unsigned) grid), dim3(threads), lds, st, x, y, p->d_chirp, p->d_xc, p->d_tw, n,
+                       n2, tpt, reverse, gf, P, Wn, conj_out, ntr, fuse ? P : 0, s2);
+  });
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
 
-// device pointers in, device pointers out; x == y allowed
+// ---- the launches that several plans share ---------------------------------------------------------------------------------
+
+// A pass of L-point columns over [L][C] on fft_cols16_kernel<PASS>: pass 1 stores transposed with the four-step twiddle, pass 2 in
+// natural order times sc.  ipitch: the row pitch of a padded input (0: C)
+void launch_cols16(const tsdgpu_fft *p, int pass, const cpx *src, cpx *dst, const cpx *tw, int L, int logL, int C, int batch, int inverse,
+                   float sc, hipStream_t st, int ipitch = 0)
+{
+  const int tpt = L / 16;
+  int CT = std::min(std::max(16, 256 / tpt), C);
+  // 2048-point columns: 8 of them fill the LDS of a CU with ONE workgroup (139 KiB) whose load, transform and store phases
+  // nothing overlaps; two workgroups of 4 columns measure 3-5 % faster (profiles/r3_fft_large_ab.txt)
+  if (L == 2048) CT = std::min(CT, 4);
+  while ((size_t) CT * (L + L / 16 + 1) * sizeof(cpx) > 150 * 1024) CT >>= 1;
+  while (CT * tpt > 1024) CT >>= 1;                                    // L = 2048 -> 8 columns, 4096 -> 4
+  const size_t lds = (size_t) CT * (L + L / 16 + 1) * sizeof(cpx);
+  const dim3 grid((unsigned) (C / CT), (unsigned) batch), blk((unsigned) (CT * tpt));
+  int_switch<1, 2>(pass, [&](auto ps) {
+    s16_radix(first_radix(logL), [&](auto r) {
+      hipLaunchKernelGGL((fft_cols16_kernel<decltype(ps)::value, decltype(r)::value>), grid, blk, lds, st, src, dst, tw, L, tpt, C, CT, p->d_thi,
+                         p->d_tlo, inverse, sc, 0, ipitch > 0 ? ipitch : C);
+    });
+  });
+}
+
+// A pass on fft1m_cols_kernel<PASS> / fft2k_cols_kernel<PASS> over `grid` persistent workgroups: the twin with the dynamic
+// hand-out where the pass has the counter (TileCounter::begin), else the one with the static partition
+template <int PASS>
+void launch_f1m(const tsdgpu_fft *p, int grid, hipStream_t st, const cpx *src, cpx *dst, int inverse, float scale, int zp, int ntiles,
+                unsigned *ctr, unsigned base, int tshift, int lc1)
+{
+  auto *kernel = ctr ? fft1m_cols_kernel<PASS, true> : fft1m_cols_kernel<PASS, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(1024), F1M_LDS, st, src, dst, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, scale, zp, ntiles, ctr,
+                     base, tshift, lc1);
+}
+template <int PASS>
+void launch_f2k(const tsdgpu_fft *p, int grid, hipStream_t st, const cpx *src, cpx *dst, int C, int ipitch, int opitch, int inverse,
+                float scale, int ntiles, unsigned *ctr, unsigned base, const cpx *ta, const cpx *td)
+{
+  auto *kernel = ctr ? fft2k_cols_kernel<PASS, true> : fft2k_cols_kernel<PASS, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), F1M_LDS, st, src, dst, p->d_w1, p->d_w2, p->d_w2k, C, ipitch, opitch, inverse, scale, ntiles,
+                     ctr, base, ta, td);
+}
+
+// ---- the steps, one function per kind: device pointers in, device pointers out; x == y allowed ---------------------------------
+int step_device(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int forward, hipStream_t st);
+
+int step_pow2_s16(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  const int n = p->n;
+  const float scale = 1.0f / std::sqrt((float) n);
+  const int tpt = n / 16, threads = std::max(256, tpt), T = threads / tpt;
+  const size_t lds = (size_t) T * (n + n / 16) * sizeof(cpx);
+  const unsigned grid = (unsigned) cdiv(batch, T);
+  const int r0 = first_radix(p->logn);
+  // one transform per workgroup and more transforms than the chip holds at once: persistent
+  // workgroups that prefetch their next transform
+  constexpr int PERSIST_MIN = 16384;   // measured: 16384 0.292 -> 0.252 ms per 2^26 points; 8192 and 4096 lose 1-10 %
+  if (n >= PERSIST_MIN && T == 1) {
+    const int per_cu = std::max(1, std::min((int) (160 * 1024 / lds), 2048 / threads));
+    if (batch > 2 * cu_count() * per_cu) {
+      const unsigned g = (unsigned) (cu_count() * per_cu);
+      s16_radix(r0, [&](auto r) {
+        hipLaunchKernelGGL((fft_s16_persistent_kernel<decltype(r)::value>), dim3(g), dim3(threads), lds, st, x, y, p->d_tw, n, tpt, inverse, scale, batch);
+      });
+      TSD_HIP(hipGetLastError());
+      return TSDGPU_OK;
+    }
+  }
+  s16_radix(r0, [&](auto r) {
+    hipLaunchKernelGGL((fft_s16_kernel<decltype(r)::value>), dim3(grid), dim3(threads), lds, st, x, y, p->d_tw, n, tpt, inverse, scale, batch,
+                       (const cpx *) nullptr);
+  });
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+int step_pow2_w1m(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  // the transposed intermediate gets a padded row pitch: its columns are read back by
+  // pass 2 with a stride that is no longer a power of two (spreads the HBM channels)
+  constexpr int ZP = 1024 + 16;
+  int rc = p->work.reserve((size_t) batch * 1024 * ZP * sizeof(cpx));
+  if (rc) return rc;
+  cpx *z = p->work.as<cpx>();
+  // persistent workgroups, one per CU (148 KiB of LDS each)
+  const int ntiles = 64 * batch, grid = std::min(ntiles, cu_count());
+  TileCounter::Pass p1{ntiles, grid}, p2{ntiles, grid};
+  if ((rc = p->ctr.begin(st, &p1, &p2))) return rc;
+  // (the two passes are dynamic together or not at all, and the static twins of this plan are handed the bases as well)
+  const unsigned b1 = p->ctr.base, b2 = b1 + (unsigned) ntiles + (unsigned) grid;
+  launch_f1m<1>(p, grid, st, x, z, inverse, 1.0f, ZP, ntiles, p1.ctr, b1, 6, 0);
+  launch_f1m<2>(p, grid, st, z, y, inverse, 1.0f / 1024.0f, ZP, ntiles, p2.ctr, b2, 6, 0);
+  return p->ctr.commit();
+}
+
+// the column count C as the tile shift of fft1m_cols_kernel: C = 16 << tshift
+int tile_shift(int C)
+{
+  int tshift = 0;
+  while ((16 << tshift) < C) tshift++;
+  return tshift;
+}
+
+// n = 2^15 .. 2^19 as 1024 x C: pass 1 on fft1m_cols_kernel<1> into a padded intermediate, pass 2 on fft_cols16_kernel<2>
+int step_4step_1k(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, float scale, hipStream_t st)
+{
+  const int C = p->N2a, zp = 1024 + 16;
+  int rc = p->work.reserve((size_t) batch * C * zp * sizeof(cpx));
+  if (rc) return rc;
+  cpx *z = p->work.as<cpx>();
+  const int64_t nt1 = (int64_t) (C / 16) * batch;
+  const int g1 = (int) std::min<int64_t>(nt1, cu_count());
+  TileCounter::Pass p1{nt1, g1};
+  if ((rc = p->ctr.begin(st, &p1))) return rc;
+  launch_f1m<1>(p, g1, st, x, z, inverse, 1.0f, zp, (int) nt1, p1.ctr, p1.base, tile_shift(C), 0);
+  if ((rc = p->ctr.commit())) return rc;
+  launch_cols16(p, 2, z, y, p->d_tw2a, p->N2a, p->logN2a, 1024, batch, inverse, scale, st, zp);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+// n = 2^23 .. 2^25 as 1024 x C1 x 1024: fft1m_cols_kernel<1>, the C1-point planes in place, fft1m_cols_kernel<2>
+int step_4step_3pass(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, float scale, hipStream_t st)
+{
+  const int C1 = p->c3, C = C1 * 1024, zp = 1024 + 16, lc1 = p->logn - 20;
+  int rc = p->work.reserve((size_t) batch * C * zp * sizeof(cpx));
+  if (rc) return rc;
+  cpx *z = p->work.as<cpx>();
+  const int64_t nt1 = (int64_t) (C / 16) * batch, nt2 = (int64_t) 64 * C1 * batch;
+  TSD_CHECK(nt1 <= 0x3fffffff && nt2 <= 0x3fffffff, "fft_step: batch %d too large for n = 2^%d", batch, p->logn);
+  const int g1 = (int) std::min<int64_t>(nt1, cu_count()), g2 = (int) std::min<int64_t>(nt2, cu_count());
+  TileCounter::Pass p1{nt1, g1}, p2{nt2, g2};
+  if ((rc = p->ctr.begin(st, &p1, &p2))) return rc;
+  launch_f1m<1>(p, g1, st, x, z, inverse, 1.0f, zp, (int) nt1, p1.ctr, p1.base, tile_shift(C), 0);
+  int_switch<8, 16, 32>(C1, [&](auto c1) {
+    constexpr int VEC = decltype(c1)::value == 32 ? 1 : 2;
+    const int64_t threads = (int64_t) batch * 1024 * (1024 / VEC);
+    hipLaunchKernelGGL((fft_planes_kernel<decltype(c1)::value, VEC>), dim3((unsigned) cdiv(threads, 256)), dim3(256), 0, st, z, p->d_tp, zp, threads);
+  });
+  launch_f1m<2>(p, g2, st, z, y, inverse, scale, zp, (int) nt2, p2.ctr, p2.base, 6, lc1);
+  return p->ctr.commit();
+}
+
+// 2048-point column passes in sixteen-column tiles held in the register file (fft2k_cols_kernel), persistent grids; the
+// 1024-point pass of 2^21 on the 2^20 plan's column kernel; a padded intermediate when both passes can take one
+int step_4step_2k(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, float scale, hipStream_t st)
+{
+  const bool p1w = p->cols2k && p->N1 == 1024, p1k = p->cols2k_p1, p2k = p->cols2k;
+  const int zp = (p2k && (p1w || p1k)) ? p->N1 + 16 : p->N1;
+  int rc = TSDGPU_OK;
+  if (zp != p->N1 && (rc = p->work.reserve((size_t) batch * p->N2 * zp * sizeof(cpx)))) return rc;
+  cpx *z = p->work.as<cpx>();
+  const int nt1 = (p->N2 / 16) * batch, g1 = std::min(nt1, cu_count()), nt2 = (p->N1 / 16) * batch, g2 = std::min(nt2, cu_count());
+  TileCounter::Pass p1{nt1, g1, p1w || p1k}, p2{nt2, g2, p2k};
+  if ((rc = p->ctr.begin(st, &p1, &p2))) return rc;
+  if (p1w) launch_f1m<1>(p, g1, st, x, z, inverse, 1.0f, zp, nt1, p1.ctr, p1.base, tile_shift(p->N2), 0);
+  else if (p1k) launch_f2k<1>(p, g1, st, x, z, p->N2, p->N2, zp, inverse, 1.0f, nt1, p1.ctr, p1.base, p->d_ta, p->d_td);
+  else launch_cols16(p, 1, x, z, p->d_tw1, p->N1, p->logN1, p->N2, batch, inverse, 1.0f, st);
+  if (p2k) launch_f2k<2>(p, g2, st, z, y, p->N1, zp, p->N1, inverse, scale, nt2, p2.ctr, p2.base, nullptr, nullptr);
+  else launch_cols16(p, 2, z, y, p->d_tw2, p->N2, p->logN2, p->N1, batch, inverse, scale, st);
+  return p->ctr.commit();
+}
+
+// both passes on fft_cols16_kernel
+int step_4step_square(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, float scale, hipStream_t st)
+{
+  cpx *z = p->work.as<cpx>();
+  launch_cols16(p, 1, x, z, p->d_tw1, p->N1, p->logN1, p->N2, batch, inverse, 1.0f, st);
+  TSD_HIP(hipGetLastError());
+  launch_cols16(p, 2, z, y, p->d_tw2, p->N2, p->logN2, p->N1, batch, inverse, scale, st);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+// TSDGPU_FFT_GENERIC: both passes on the radix-2 column kernel
+int step_4step_generic(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, float scale, hipStream_t st)
+{
+  cpx *z = p->work.as<cpx>();
+  // x viewed [N1][N2]: pass 1 = column FFTs (length N1) + twiddle, stored transposed [N2][N1]
+  int tile1 = COL_TILE, tile2 = COL_TILE;
+  while ((size_t) tile1 * (p->N1 + 1) * sizeof(cpx) > 150 * 1024) tile1 >>= 1;
+  while ((size_t) tile2 * (p->N2 + 1) * sizeof(cpx) > 150 * 1024) tile2 >>= 1;
+  hipLaunchKernelGGL(fft_cols_kernel<true>, dim3((unsigned) cdiv(p->N2, tile1), (unsigned) batch), dim3(FFT_THREADS),
+                     (size_t) tile1 * (p->N1 + 1) * sizeof(cpx), st, x, z, p->d_tw1, p->N1, p->logN1, p->N2,
+                     p->d_thi, p->d_tlo, inverse, 1.0f, tile1);
+  TSD_HIP(hipGetLastError());
+  // z viewed [N2][N1]: pass 2 = column FFTs (length N2), natural store: y[k2 * N1 + k1]
+  hipLaunchKernelGGL(fft_cols_kernel<false>, dim3((unsigned) cdiv(p->N1, tile2), (unsigned) batch), dim3(FFT_THREADS),
+                     (size_t) tile2 * (p->N2 + 1) * sizeof(cpx), st, z, y, p->d_tw2, p->N2, p->logN2, p->N1,
+                     p->d_thi, p->d_tlo, inverse, scale, tile2);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+// x viewed [N1][N2]: pass 1 = column FFTs (length N1) + twiddle, stored transposed [N2][N1];
+// z viewed [N2][N1]: pass 2 = column FFTs (length N2), natural store y[k2 * N1 + k1].  The sub-plans in the order they are tried.
+int step_pow2_4step(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  const int64_t total = (int64_t) p->n * batch;
+  TSD_CHECK(batch <= 65535, "fft_step: batch %d too large for the four-step path (max 65535 per call)", batch);
+  const int rc = p->work.reserve((size_t) total * sizeof(cpx));
+  if (rc) return rc;
+  const float scale = 1.0f / std::sqrt((float) p->n);
+  static const bool generic = dev_switch("FFT_GENERIC") != nullptr;
+  if (generic) return step_4step_generic(p, x, y, batch, inverse, scale, st);
+  if (p->p1k1 && total >= (p->logn >= 18 ? (int64_t) 1 << 19 : (int64_t) 1 << 21)) return step_4step_1k(p, x, y, batch, inverse, scale, st);
+  if (p->c3) return step_4step_3pass(p, x, y, batch, inverse, scale, st);
+  if (p->cols2k || p->cols2k_p1) return step_4step_2k(p, x, y, batch, inverse, scale, st);
+  return step_4step_square(p, x, y, batch, inverse, scale, st);
+}
+
+int step_oddpow2(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  const int n = p->n, m = p->mix_m, P = p->mix_P, tpt = P / 16, per = m * tpt;
+  const int T = std::max(1, 256 / per), threads = T * per;
+  const size_t lds = (size_t) T * m * (P + P / 16) * sizeof(cpx);
+  const unsigned grid = (unsigned) cdiv(batch, T);
+  const float sc = 1.0f / std::sqrt((float) n);
+  s16_radix(first_radix(p->logn), [&](auto r) {
+    int_switch<4, 8, 16>(m <= 3 ? 4 : m <= 7 ? 8 : 16, [&](auto mm) {
+      hipLaunchKernelGGL((fft_oddpow2_kernel<decltype(r)::value, decltype(mm)::value>), dim3(grid), dim3(threads), lds, st, x, y, p->d_tw, p->d_wm,
+                         p->d_rot, m, P, tpt, inverse, sc, batch);
+    });
+  });
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+int step_mixed(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  const int m = p->mix_m, P = p->mix_P;
+  TSD_CHECK(batch <= 65535, "fft_step: batch %d too large for the mixed-radix path (max 65535 per call)", batch);
+  int rc = p->work.reserve((size_t) p->n * batch * sizeof(cpx));
+  if (rc) return rc;
+  cpx *z = p->work.as<cpx>();
+  const int64_t tot1 = (int64_t) batch * P;
+  const float s2 = 1.0f / std::sqrt((float) P);
+  // pass 1: Z[b][r][k1] = W_n^(r k1) * (unitary m-point DFT of x[b][r + P i])
+  if (m <= 31) {
+    const unsigned g1 = (unsigned) cdiv(tot1, 256);
+    const float s1 = 1.0f / std::sqrt((float) m);
+    int_switch<8, 16, 32>(m <= 8 ? 8 : m <= 16 ? 16 : 32, [&](auto mm) {
+      hipLaunchKernelGGL((fft_odd_dft_kernel<decltype(mm)::value>), dim3(g1), dim3(256), (size_t) (32 + 256 * m) * sizeof(cpx), st, x, z, p->d_wm, p->d_rot,
+                         m, P, inverse, s1, tot1);
+    });
+    TSD_HIP(hipGetLastError());
+  } else if (bluestein_fusable(p->sub, P)) {
+    return launch_bluestein(p->sub, x, y, tot1, inverse, inverse, P, p->d_rot, st, true);      // both passes in one kernel
+  } else {
+    rc = launch_bluestein(p->sub, x, z, tot1, inverse, inverse, P, p->d_rot, st);
+    if (rc) return rc;
+  }
+  // pass 2: P-point column FFTs over r, natural-order store
+  if (P < 16) {
+    const int64_t tot2 = (int64_t) batch * m;
+    const unsigned g2 = (unsigned) cdiv(tot2, 256);
+    int_switch<2, 4, 8>(P, [&](auto pp) {
+      hipLaunchKernelGGL((fft_smallcols_kernel<decltype(pp)::value>), dim3(g2), dim3(256), 0, st, z, y, m, inverse, s2, tot2);
+    });
+    TSD_HIP(hipGetLastError());
+    return TSDGPU_OK;
+  }
+  const int tpt = P / 16;
+  // ragged tiles: any column count works; no wider than the m live columns
+  int CT = std::min(std::min(16, m), 1024 / tpt);
+  while ((size_t) CT * (P + P / 16 + 1) * sizeof(cpx) > 150 * 1024) CT--;
+  const size_t lds = (size_t) CT * (P + P / 16 + 1) * sizeof(cpx);
+  const dim3 grid((unsigned) cdiv(m, CT), (unsigned) batch), blk((unsigned) (CT * tpt));
+  s16_radix(first_radix(p->logn), [&](auto r) {
+    hipLaunchKernelGGL((fft_cols16_kernel<2, decltype(r)::value>), grid, blk, lds, st, z, y, p->d_tw, P, tpt, m, CT, nullptr, nullptr, inverse, s2, 1, m);
+  });
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+int step_even(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int forward, hipStream_t st)
+{
+  const int n = p->n;
+  const int64_t total = (int64_t) n * batch;
+  int rc = p->work.reserve((size_t) total * sizeof(cpx));
+  if (rc) return rc;
+  rc = p->work2.reserve((size_t) total * sizeof(cpx));
+  if (rc) return rc;
+  cpx *t1 = p->work.as<cpx>(), *t2 = p->work2.as<cpx>();
+  hipLaunchKernelGGL(fft_split_eo_kernel, dim3(blocks_for(total)), dim3(256), 0, st, x, t1, n, total);
+  TSD_HIP(hipGetLastError());
+  rc = step_device(p->sub, t1, t2, 2 * batch, forward, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fft_combine_eo_kernel, dim3(blocks_for(total)), dim3(256), 0, st, t2, y, p->d_rot, n, forward ? 0 : 1, total);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
+int step_odd(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int inverse, hipStream_t st)
+{
+  const int n = p->n, n2 = p->n2;
+  if (p->blu_fused)                                         // (in place is fine: a workgroup loads its whole transforms before it stores)
+    return launch_bluestein(p, x, y, batch, inverse, 0, 1, nullptr, st);
+  const int64_t total = (int64_t) n * batch, tot2 = (int64_t) n2 * batch;
+  int rc = p->work.reserve((size_t) tot2 * sizeof(cpx));
+  if (rc) return rc;
+  rc = p->work2.reserve((size_t) tot2 * sizeof(cpx));
+  if (rc) return rc;
+  cpx *a = p->work.as<cpx>(), *b = p->work2.as<cpx>();
+  hipLaunchKernelGGL(czt_pre_kernel, dim3(blocks_for(tot2)), dim3(256), 0, st, x, a, p->d_chirp, n, n2, tot2);
+  TSD_HIP(hipGetLastError());
+  rc = step_device(p->sub, a, b, batch, 1, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(czt_mul_kernel, dim3(blocks_for(tot2)), dim3(256), 0, st, b, p->d_xc, n2, tot2);
+  TSD_HIP(hipGetLastError());
+  rc = step_device(p->sub, b, a, batch, 0, st);
+  if (rc) return rc;
+  const float g = std::sqrt((float) n2) / std::sqrt((float) n);
+  hipLaunchKernelGGL(czt_post_kernel, dim3(blocks_for(total)), dim3(256), 0, st, a, y, p->d_chirp, n, n2, g, inverse, total);
+  TSD_HIP(hipGetLastError());
+  return TSDGPU_OK;
+}
+
 int step_device(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int forward, hipStream_t st)
 {
   const int n = p->n;
   const int inverse = forward ? 0 : 1;
-  const int64_t total = (int64_t) n * batch;
   if (batch > 65535 && (p->kind == tsdgpu_fft::MIXED || p->kind == tsdgpu_fft::POW2_4STEP)) {
     // these plans put the batch index in gridDim.y: larger batches go in slices
     for (int b0 = 0; b0 < batch; b0 += 65535) {
@@ -2508,286 +2846,16 @@ int step_device(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int forward, hip
   }
   switch (p->kind) {
     case tsdgpu_fft::ONE:
-      if (x != y) TSD_HIP(hipMemcpyAsync(y, x, (size_t) total * sizeof(cpx), hipMemcpyDeviceToDevice, st));
+      if (x != y) TSD_HIP(hipMemcpyAsync(y, x, (size_t) n * batch * sizeof(cpx), hipMemcpyDeviceToDevice, st));
       return TSDGPU_OK;
-    case tsdgpu_fft::POW2_LDS: {
-      const float scale = 1.0f / std::sqrt((float) n);
-      hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned) batch), dim3(FFT_THREADS), (size_t) n * sizeof(cpx), st, x,
-                         y, p->d_tw, n, p->logn, inverse, scale);
+    case tsdgpu_fft::POW2_LDS:
+      hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned) batch), dim3(FFT_THREADS), (size_t) n * sizeof(cpx), st, x, y, p->d_tw, n, p->logn,
+                         inverse, 1.0f / std::sqrt((float) n));
       TSD_HIP(hipGetLastError());
       return TSDGPU_OK;
-    }
-    case tsdgpu_fft::POW2_S16: {
-      const float scale = 1.0f / std::sqrt((float) n);
-      const int tpt = n / 16, threads = std::max(256, tpt), T = threads / tpt;
-      const size_t lds = (size_t) T * (n + n / 16) * sizeof(cpx);
-      const unsigned grid = (unsigned) cdiv(batch, T);
-      const int r0 = 1 << ((p->logn & 3) == 0 ? 4 : (p->logn & 3));
-      // one transform per workgroup and more transforms than the chip holds at once: persistent
-      // workgroups that prefetch their next transform
-      constexpr int PERSIST_MIN = 16384;   // measured: 16384 0.292 -> 0.252 ms per 2^26 points; 8192 and 4096 lose 1-10 %
-      if (n >= PERSIST_MIN && T == 1) {
-        static const int NCU = [] {
-          int dev = 0, c = 256;
-          if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-          return c > 0 ? c : 256;
-        }();
-        const int per_cu = std::max(1, std::min((int) (160 * 1024 / lds), 2048 / threads));
-        if (batch > 2 * NCU * per_cu) {
-          const unsigned g = (unsigned) (NCU * per_cu);
-#define S16P_LAUNCH(R) hipLaunchKernelGGL((fft_s16_persistent_kernel<R>), dim3(g), dim3(threads), lds, st, x, y, p->d_tw, n, tpt, inverse, scale, batch)
-          if (r0 == 16) S16P_LAUNCH(16); else if (r0 == 8) S16P_LAUNCH(8); else if (r0 == 4) S16P_LAUNCH(4); else S16P_LAUNCH(2);
-#undef S16P_LAUNCH
-          TSD_HIP(hipGetLastError());
-          return TSDGPU_OK;
-        }
-      }
-#define S16_LAUNCH(R) hipLaunchKernelGGL((fft_s16_kernel<R>), dim3(grid), dim3(threads), lds, st, x, y, p->d_tw, n, tpt, inverse, scale, batch, (const cpx *) nullptr)
-      if (r0 == 16) S16_LAUNCH(16); else if (r0 == 8) S16_LAUNCH(8); else if (r0 == 4) S16_LAUNCH(4); else S16_LAUNCH(2);
-#undef S16_LAUNCH
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::POW2_W1024: {
-      const float scale = 1.0f / 32.0f;
-      hipLaunchKernelGGL(fft1024_rows_kernel, dim3((unsigned) cdiv(batch, 4)), dim3(256), 0, st, x, y, p->d_w1, p->d_w2,
-                         inverse, scale, batch);
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::POW2_W1M: {
-      // the transposed intermediate gets a padded row pitch: its columns are read back by
-      // pass 2 with a stride that is no longer a power of two (spreads the HBM channels)
-      constexpr int ZP = 1024 + 16;
-      int rc = p->work.reserve((size_t) batch * 1024 * ZP * sizeof(cpx));
-      if (rc) return rc;
-      cpx *z = p->work.as<cpx>();
-      // persistent workgroups, one per CU (148 KiB of LDS each); tiles are dealt round-robin
-      const int ntiles = 64 * batch;
-      static const int NCU = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-      }();
-      const int GRID = NCU;
-      const int grid = std::min(ntiles, GRID);
-      // dynamic tile hand-out when every workgroup gets several tiles (TSDGPU_FFT_DYN=0: the static partition)
-      const char *dyn_s = dev_switch("FFT_DYN");
-      // (not while `st` records a graph: the base is a launch argument, a replay would see a spent counter and write nothing)
-      unsigned *ctr = (p->d_ctr && ntiles >= 4 * grid && !(dyn_s && atoi(dyn_s) == 0) && !stream_is_capturing(st)) ? p->d_ctr : nullptr;
-      if (ctr && p->ctr_stale) {
-        TSD_HIP(hipMemsetAsync(p->d_ctr, 0, 256, st));
-        p->ctr_base = 0;
-        p->ctr_stale = false;
-      }
-      const unsigned b1 = p->ctr_base, b2 = b1 + (unsigned) ntiles + (unsigned) grid;
-      if (ctr) {
-        hipLaunchKernelGGL((fft1m_cols_kernel<1, true>), dim3(grid), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta,
-                           p->d_td, inverse, 1.0f, ZP, ntiles, ctr, b1, 6, 0);
-        hipLaunchKernelGGL((fft1m_cols_kernel<2, true>), dim3(grid), dim3(1024), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_ta,
-                           p->d_td, inverse, 1.0f / 1024.0f, ZP, ntiles, ctr, b2, 6, 0);
-      } else {
-        hipLaunchKernelGGL((fft1m_cols_kernel<1, false>), dim3(grid), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta,
-                           p->d_td, inverse, 1.0f, ZP, ntiles, ctr, b1, 6, 0);
-        hipLaunchKernelGGL((fft1m_cols_kernel<2, false>), dim3(grid), dim3(1024), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_ta,
-                           p->d_td, inverse, 1.0f / 1024.0f, ZP, ntiles, ctr, b2, 6, 0);
-      }
-      if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
-        if (ctr) p->ctr_stale = true;                    // (the device counter and the host base may have parted)
-        return set_err(TSDGPU_ERR_HIP, "fft_step: launch failed: %s", hipGetErrorString(le));
-      }
-      if (ctr) p->ctr_base = b2 + (unsigned) ntiles + (unsigned) grid;
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::POW2_4STEP: {
-      TSD_CHECK(batch <= 65535, "fft_step: batch %d too large for the four-step path (max 65535 per call)", batch);
-      int rc = p->work.reserve((size_t) total * sizeof(cpx));
-      if (rc) return rc;
-      cpx *z = p->work.as<cpx>();
-      const float scale = 1.0f / std::sqrt((float) n);
-      // x viewed [N1][N2]: pass 1 = column FFTs (length N1) + twiddle, stored transposed [N2][N1];
-      // z viewed [N2][N1]: pass 2 = column FFTs (length N2), natural store y[k2 * N1 + k1]
-      static const bool generic = dev_switch("FFT_GENERIC") != nullptr;
-      if (!generic) {
-        auto launch = [&](int pass, const cpx *src, cpx *dst, const cpx *tw, int L, int logL, int C, float sc, int ipitch = 0) {
-          const int tpt = L / 16;
-          int CT = std::min(std::max(16, 256 / tpt), C);
-          // 2048-point columns: 8 of them fill the LDS of a CU with ONE workgroup (139 KiB) whose load, transform and store phases
-          // nothing overlaps; two workgroups of 4 columns measure 3-5 % faster (profiles/r3_fft_large_ab.txt)
-          if (L == 2048) CT = std::min(CT, 4);
-          while ((size_t) CT * (L + L / 16 + 1) * sizeof(cpx) > 150 * 1024) CT >>= 1;
-          while (CT * tpt > 1024) CT >>= 1;                                    // L = 2048 -> 8 columns, 4096 -> 4
-          const size_t lds = (size_t) CT * (L + L / 16 + 1) * sizeof(cpx);
-          const dim3 grid((unsigned) (C / CT), (unsigned) batch), blk((unsigned) (CT * tpt));
-          const int r0 = 1 << ((logL & 3) == 0 ? 4 : (logL & 3));
-#define C16_LAUNCH(P, R) hipLaunchKernelGGL((fft_cols16_kernel<P, R>), grid, blk, lds, st, src, dst, tw, L, tpt, C, CT, p->d_thi, p->d_tlo, inverse, sc, 0, ipitch > 0 ? ipitch : C)
-          if (pass == 1) {
-            if (r0 == 16) C16_LAUNCH(1, 16); else if (r0 == 8) C16_LAUNCH(1, 8); else if (r0 == 4) C16_LAUNCH(1, 4); else C16_LAUNCH(1, 2);
-          } else {
-            if (r0 == 16) C16_LAUNCH(2, 16); else if (r0 == 8) C16_LAUNCH(2, 8); else if (r0 == 4) C16_LAUNCH(2, 4); else C16_LAUNCH(2, 2);
-          }
-#undef C16_LAUNCH
-        };
-        if (p->p1k1 && total >= (p->logn >= 18 ? (int64_t) 1 << 19 : (int64_t) 1 << 21)) {
-          const int C = p->N2a, zp = 1024 + 16;
-          rc = p->work.reserve((size_t) batch * C * zp * sizeof(cpx));
-          if (rc) return rc;
-          z = p->work.as<cpx>();
-          const int ncu = cu_count();
-          const int64_t nt1 = (int64_t) (C / 16) * batch;
-          const int g1 = (int) std::min<int64_t>(nt1, ncu);
-          const bool dyn_ok = p->d_ctr && dev_switch_int("FFT_DYN", 1) != 0 && !stream_is_capturing(st);
-          unsigned *c1 = (dyn_ok && nt1 >= 4 * g1) ? p->d_ctr : nullptr;
-          if (c1 && p->ctr_stale) {
-            TSD_HIP(hipMemsetAsync(p->d_ctr, 0, 256, st));
-            p->ctr_base = 0;
-            p->ctr_stale = false;
-          }
-          const unsigned b1 = p->ctr_base;
-          int tshift = 0;
-          while ((16 << tshift) < C) tshift++;
-          if (c1)
-            hipLaunchKernelGGL((fft1m_cols_kernel<1, true>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                               (int) nt1, c1, b1, tshift, 0);
-          else
-            hipLaunchKernelGGL((fft1m_cols_kernel<1, false>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                               (int) nt1, (unsigned *) nullptr, 0u, tshift, 0);
-          if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
-            if (c1) p->ctr_stale = true;
-            return set_err(TSDGPU_ERR_HIP, "fft_step: launch failed: %s", hipGetErrorString(le));
-          }
-          if (c1) p->ctr_base = b1 + (unsigned) nt1 + (unsigned) g1;
-          launch(2, z, y, p->d_tw2a, p->N2a, p->logN2a, 1024, scale, zp);
-          TSD_HIP(hipGetLastError());
-          return TSDGPU_OK;
-        }
-        if (p->c3) {
-          const int C1 = p->c3, C = C1 * 1024, zp = 1024 + 16, lc1 = p->logn - 20;
-          rc = p->work.reserve((size_t) batch * C * zp * sizeof(cpx));
-          if (rc) return rc;
-          z = p->work.as<cpx>();
-          const int ncu = cu_count();
-          const int64_t nt1 = (int64_t) (C / 16) * batch, nt2 = (int64_t) 64 * C1 * batch;
-          TSD_CHECK(nt1 <= 0x3fffffff && nt2 <= 0x3fffffff, "fft_step: batch %d too large for n = 2^%d", batch, p->logn);
-          const int g1 = (int) std::min<int64_t>(nt1, ncu), g2 = (int) std::min<int64_t>(nt2, ncu);
-          const bool dyn_ok = p->d_ctr && dev_switch_int("FFT_DYN", 1) != 0 && !stream_is_capturing(st);
-          unsigned *c1 = (dyn_ok && nt1 >= 4 * g1) ? p->d_ctr : nullptr, *c2 = (dyn_ok && nt2 >= 4 * g2) ? p->d_ctr : nullptr;
-          if ((c1 || c2) && p->ctr_stale) {
-            TSD_HIP(hipMemsetAsync(p->d_ctr, 0, 256, st));
-            p->ctr_base = 0;
-            p->ctr_stale = false;
-          }
-          const unsigned b1 = p->ctr_base, b2 = b1 + (c1 ? (unsigned) nt1 + (unsigned) g1 : 0u);
-          int tshift = 0;
-          while ((16 << tshift) < C) tshift++;
-          if (c1)
-            hipLaunchKernelGGL((fft1m_cols_kernel<1, true>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                               (int) nt1, c1, b1, tshift, 0);
-          else
-            hipLaunchKernelGGL((fft1m_cols_kernel<1, false>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                               (int) nt1, (unsigned *) nullptr, 0u, tshift, 0);
-          {
-            const int vec = C1 == 32 ? 1 : 2;
-            const int64_t threads = (int64_t) batch * 1024 * (1024 / vec);
-            const unsigned gp = (unsigned) cdiv(threads, 256);
-            if (C1 == 8) hipLaunchKernelGGL((fft_planes_kernel<8, 2>), dim3(gp), dim3(256), 0, st, z, p->d_tp, zp, threads);
-            else if (C1 == 16) hipLaunchKernelGGL((fft_planes_kernel<16, 2>), dim3(gp), dim3(256), 0, st, z, p->d_tp, zp, threads);
-            else hipLaunchKernelGGL((fft_planes_kernel<32, 1>), dim3(gp), dim3(256), 0, st, z, p->d_tp, zp, threads);
-          }
-          if (c2)
-            hipLaunchKernelGGL((fft1m_cols_kernel<2, true>), dim3(g2), dim3(1024), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, scale, zp,
-                               (int) nt2, c2, b2, 6, lc1);
-          else
-            hipLaunchKernelGGL((fft1m_cols_kernel<2, false>), dim3(g2), dim3(1024), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, scale, zp,
-                               (int) nt2, (unsigned *) nullptr, 0u, 6, lc1);
-          if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
-            if (c1 || c2) p->ctr_stale = true;
-            return set_err(TSDGPU_ERR_HIP, "fft_step: launch failed: %s", hipGetErrorString(le));
-          }
-          p->ctr_base = b2 + (c2 ? (unsigned) nt2 + (unsigned) g2 : 0u);
-          return TSDGPU_OK;
-        }
-        if (p->cols2k || p->cols2k_p1) {
-          // 2048-point column passes in sixteen-column tiles held in the register file (fft2k_cols_kernel), persistent grids; the
-          // 1024-point pass of 2^21 on the 2^20 plan's column kernel; a padded intermediate when both passes can take one
-          static const int NCU2 = [] {
-            int dev = 0, nn = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev);
-            return nn > 0 ? nn : 256;
-          }();
-          const bool p1w = p->cols2k && p->N1 == 1024, p1k = p->cols2k_p1, p2k = p->cols2k;
-          const int zp = (p2k && (p1w || p1k)) ? p->N1 + 16 : p->N1;
-          if (zp != p->N1) {
-            rc = p->work.reserve((size_t) batch * p->N2 * zp * sizeof(cpx));
-            if (rc) return rc;
-            z = p->work.as<cpx>();
-          }
-          const int nt1 = (p->N2 / 16) * batch, g1 = std::min(nt1, NCU2), nt2 = (p->N1 / 16) * batch, g2 = std::min(nt2, NCU2);
-          const bool dyn_ok = p->d_ctr && dev_switch_int("FFT_DYN", 1) != 0 && !stream_is_capturing(st);
-          unsigned *c1 = ((p1w || p1k) && dyn_ok && nt1 >= 4 * g1) ? p->d_ctr : nullptr, *c2 = (p2k && dyn_ok && nt2 >= 4 * g2) ? p->d_ctr : nullptr;
-          if ((c1 || c2) && p->ctr_stale) {
-            TSD_HIP(hipMemsetAsync(p->d_ctr, 0, 256, st));
-            p->ctr_base = 0;
-            p->ctr_stale = false;
-          }
-          const unsigned b1 = p->ctr_base, b2 = b1 + (c1 ? (unsigned) nt1 + (unsigned) g1 : 0u);
-          if (p1w) {
-            int tshift = 0;
-            while ((16 << tshift) < p->N2) tshift++;
-            if (c1)
-              hipLaunchKernelGGL((fft1m_cols_kernel<1, true>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                                 nt1, c1, b1, tshift, 0);
-            else
-              hipLaunchKernelGGL((fft1m_cols_kernel<1, false>), dim3(g1), dim3(1024), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_ta, p->d_td, inverse, 1.0f, zp,
-                                 nt1, (unsigned *) nullptr, 0u, tshift, 0);
-          } else if (p1k) {
-            if (c1)
-              hipLaunchKernelGGL((fft2k_cols_kernel<1, true>), dim3(g1), dim3(512), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_w2k, p->N2, p->N2, zp,
-                                 inverse, 1.0f, nt1, c1, b1, p->d_ta, p->d_td);
-            else
-              hipLaunchKernelGGL((fft2k_cols_kernel<1, false>), dim3(g1), dim3(512), F1M_LDS, st, x, z, p->d_w1, p->d_w2, p->d_w2k, p->N2, p->N2, zp,
-                                 inverse, 1.0f, nt1, (unsigned *) nullptr, 0u, p->d_ta, p->d_td);
-          } else {
-            launch(1, x, z, p->d_tw1, p->N1, p->logN1, p->N2, 1.0f);
-          }
-          if (p2k) {
-            if (c2)
-              hipLaunchKernelGGL((fft2k_cols_kernel<2, true>), dim3(g2), dim3(512), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_w2k, p->N1, zp, p->N1,
-                                 inverse, scale, nt2, c2, b2, (const cpx *) nullptr, (const cpx *) nullptr);
-            else
-              hipLaunchKernelGGL((fft2k_cols_kernel<2, false>), dim3(g2), dim3(512), F1M_LDS, st, z, y, p->d_w1, p->d_w2, p->d_w2k, p->N1, zp, p->N1,
-                                 inverse, scale, nt2, (unsigned *) nullptr, 0u, (const cpx *) nullptr, (const cpx *) nullptr);
-          } else {
-            launch(2, z, y, p->d_tw2, p->N2, p->logN2, p->N1, scale);
-          }
-          if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
-            if (c1 || c2) p->ctr_stale = true;
-            return set_err(TSDGPU_ERR_HIP, "fft_step: launch failed: %s", hipGetErrorString(le));
-          }
-          p->ctr_base = b2 + (c2 ? (unsigned) nt2 + (unsigned) g2 : 0u);
-          return TSDGPU_OK;
-        }
-        launch(1, x, z, p->d_tw1, p->N1, p->logN1, p->N2, 1.0f);
-        TSD_HIP(hipGetLastError());
-        launch(2, z, y, p->d_tw2, p->N2, p->logN2, p->N1, scale);
-        TSD_HIP(hipGetLastError());
-        return TSDGPU_OK;
-      }
-      // x viewed [N1][N2]: pass 1 = column FFTs (length N1) + twiddle, stored transposed [N2][N1]
-      int tile1 = COL_TILE, tile2 = COL_TILE;
-      while ((size_t) tile1 * (p->N1 + 1) * sizeof(cpx) > 150 * 1024) tile1 >>= 1;
-      while ((size_t) tile2 * (p->N2 + 1) * sizeof(cpx) > 150 * 1024) tile2 >>= 1;
-      hipLaunchKernelGGL(fft_cols_kernel<true>, dim3((unsigned) cdiv(p->N2, tile1), (unsigned) batch), dim3(FFT_THREADS),
-                         (size_t) tile1 * (p->N1 + 1) * sizeof(cpx), st, x, z, p->d_tw1, p->N1, p->logN1, p->N2,
-                         p->d_thi, p->d_tlo, inverse, 1.0f, tile1);
-      TSD_HIP(hipGetLastError());
-      // z viewed [N2][N1]: pass 2 = column FFTs (length N2), natural store: y[k2 * N1 + k1]
-      hipLaunchKernelGGL(fft_cols_kernel<false>, dim3((unsigned) cdiv(p->N1, tile2), (unsigned) batch), dim3(FFT_THREADS),
-                         (size_t) tile2 * (p->N2 + 1) * sizeof(cpx), st, z, y, p->d_tw2, p->N2, p->logN2, p->N1,
-                         p->d_thi, p->d_tlo, inverse, scale, tile2);
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
+    case tsdgpu_fft::POW2_S16: return step_pow2_s16(p, x, y, batch, inverse, st);
+    case tsdgpu_fft::POW2_W1M: return step_pow2_w1m(p, x, y, batch, inverse, st);
+    case tsdgpu_fft::POW2_4STEP: return step_pow2_4step(p, x, y, batch, inverse, st);
     case tsdgpu_fft::SMOOTH: {
       const int tpt = p->mr_tpt, T = std::max(1, 256 / tpt), threads = T * tpt;
       const size_t lds = (size_t) T * (n + n / 16 + 1) * sizeof(cpx);
@@ -2796,109 +2864,93 @@ int step_device(tsdgpu_fft *p, const cpx *x, cpx *y, int batch, int forward, hip
       TSD_HIP(hipGetLastError());
       return TSDGPU_OK;
     }
-    case tsdgpu_fft::ODDPOW2: {
-      const int m = p->mix_m, P = p->mix_P, tpt = P / 16, per = m * tpt;
-      const int T = std::max(1, 256 / per), threads = T * per;
-      const size_t lds = (size_t) T * m * (P + P / 16) * sizeof(cpx);
-      const int r0 = 1 << ((p->logn & 3) == 0 ? 4 : (p->logn & 3));
-      const unsigned grid = (unsigned) cdiv(batch, T);
-      const float sc = 1.0f / std::sqrt((float) n);
-#define OP_LAUNCH(R, MM) hipLaunchKernelGGL((fft_oddpow2_kernel<R, MM>), dim3(grid), dim3(threads), lds, st, x, y, p->d_tw, p->d_wm, p->d_rot, m, P, tpt, inverse, sc, batch)
-#define OP_PICK(R) do { if (m <= 3) OP_LAUNCH(R, 4); else if (m <= 7) OP_LAUNCH(R, 8); else OP_LAUNCH(R, 16); } while (0)
-      if (r0 == 16) OP_PICK(16); else if (r0 == 8) OP_PICK(8); else if (r0 == 4) OP_PICK(4); else OP_PICK(2);
-#undef OP_PICK
-#undef OP_LAUNCH
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::MIXED: {
-      const int m = p->mix_m, P = p->mix_P;
-      TSD_CHECK(batch <= 65535, "fft_step: batch %d too large for the mixed-radix path (max 65535 per call)", batch);
-      int rc = p->work.reserve((size_t) total * sizeof(cpx));
-      if (rc) return rc;
-      cpx *z = p->work.as<cpx>();
-      const int64_t tot1 = (int64_t) batch * P;
-      const float s2 = 1.0f / std::sqrt((float) P);
-      // pass 1: Z[b][r][k1] = W_n^(r k1) * (unitary m-point DFT of x[b][r + P i])
-      if (m <= 31) {
-        const unsigned g1 = (unsigned) cdiv(tot1, 256);
-        const float s1 = 1.0f / std::sqrt((float) m);
-#define ODD_LAUNCH(M) hipLaunchKernelGGL((fft_odd_dft_kernel<M>), dim3(g1), dim3(256), (size_t) (32 + 256 * m) * sizeof(cpx), st, x, z, p->d_wm, p->d_rot, m, P, inverse, s1, tot1)
-        if (m <= 8) ODD_LAUNCH(8); else if (m <= 16) ODD_LAUNCH(16); else ODD_LAUNCH(32);
-#undef ODD_LAUNCH
-        TSD_HIP(hipGetLastError());
-      } else if (bluestein_fusable(p->sub, P)) {
-        return launch_bluestein(p->sub, x, y, tot1, inverse, inverse, P, p->d_rot, st, true);      // both passes in one kernel
-      } else {
-        rc = launch_bluestein(p->sub, x, z, tot1, inverse, inverse, P, p->d_rot, st);
-        if (rc) return rc;
-      }
-      // pass 2: P-point column FFTs over r, natural-order store
-      if (P < 16) {
-        const int64_t tot2 = (int64_t) batch * m;
-        const unsigned g2 = (unsigned) cdiv(tot2, 256);
-        if (P == 2) hipLaunchKernelGGL((fft_smallcols_kernel<2>), dim3(g2), dim3(256), 0, st, z, y, m, inverse, s2, tot2);
-        else if (P == 4) hipLaunchKernelGGL((fft_smallcols_kernel<4>), dim3(g2), dim3(256), 0, st, z, y, m, inverse, s2, tot2);
-        else hipLaunchKernelGGL((fft_smallcols_kernel<8>), dim3(g2), dim3(256), 0, st, z, y, m, inverse, s2, tot2);
-        TSD_HIP(hipGetLastError());
-        return TSDGPU_OK;
-      }
-      const int tpt = P / 16;
-      // ragged tiles: any column count works; no wider than the m live columns
-      int CT = std::min(std::min(16, m), 1024 / tpt);
-      while ((size_t) CT * (P + P / 16 + 1) * sizeof(cpx) > 150 * 1024) CT--;
-      const size_t lds = (size_t) CT * (P + P / 16 + 1) * sizeof(cpx);
-      const dim3 grid((unsigned) cdiv(m, CT), (unsigned) batch), blk((unsigned) (CT * tpt));
-      const int r0 = 1 << ((p->logn & 3) == 0 ? 4 : (p->logn & 3));
-#define C16_LAUNCH(R) hipLaunchKernelGGL((fft_cols16_kernel<2, R>), grid, blk, lds, st, z, y, p->d_tw, P, tpt, m, CT, nullptr, nullptr, inverse, s2, 1, m)
-      if (r0 == 16) C16_LAUNCH(16); else if (r0 == 8) C16_LAUNCH(8); else if (r0 == 4) C16_LAUNCH(4); else C16_LAUNCH(2);
-#undef C16_LAUNCH
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::EVEN: {
-      int rc = p->work.reserve((size_t) total * sizeof(cpx));
-      if (rc) return rc;
-      rc = p->work2.reserve((size_t) total * sizeof(cpx));
-      if (rc) return rc;
-      cpx *t1 = p->work.as<cpx>(), *t2 = p->work2.as<cpx>();
-      hipLaunchKernelGGL(fft_split_eo_kernel, dim3(blocks_for(total)), dim3(256), 0, st, x, t1, n, total);
-      TSD_HIP(hipGetLastError());
-      rc = step_device(p->sub, t1, t2, 2 * batch, forward, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(fft_combine_eo_kernel, dim3(blocks_for(total)), dim3(256), 0, st, t2, y, p->d_rot, n, inverse,
-                         total);
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
-    case tsdgpu_fft::ODD: {
-      const int n2 = p->n2;
-      if (p->blu_fused) {                                       // (in place is fine: a workgroup loads its whole transforms before it stores)
-        const int rc2 = launch_bluestein(p, x, y, batch, inverse, 0, 1, nullptr, st);
-        return rc2;
-      }
-      const int64_t tot2 = (int64_t) n2 * batch;
-      int rc = p->work.reserve((size_t) tot2 * sizeof(cpx));
-      if (rc) return rc;
-      rc = p->work2.reserve((size_t) tot2 * sizeof(cpx));
-      if (rc) return rc;
-      cpx *a = p->work.as<cpx>(), *b = p->work2.as<cpx>();
-      hipLaunchKernelGGL(czt_pre_kernel, dim3(blocks_for(tot2)), dim3(256), 0, st, x, a, p->d_chirp, n, n2, tot2);
-      TSD_HIP(hipGetLastError());
-      rc = step_device(p->sub, a, b, batch, 1, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(czt_mul_kernel, dim3(blocks_for(tot2)), dim3(256), 0, st, b, p->d_xc, n2, tot2);
-      TSD_HIP(hipGetLastError());
-      rc = step_device(p->sub, b, a, batch, 0, st);
-      if (rc) return rc;
-      const float g = std::sqrt((float) n2) / std::sqrt((float) n);
-      hipLaunchKernelGGL(czt_post_kernel, dim3(blocks_for(total)), dim3(256), 0, st, a, y, p->d_chirp, n, n2, g, inverse,
-                         total);
-      TSD_HIP(hipGetLastError());
-      return TSDGPU_OK;
-    }
+    case tsdgpu_fft::ODDPOW2: return step_oddpow2(p, x, y, batch, inverse, st);
+    case tsdgpu_fft::MIXED: return step_mixed(p, x, y, batch, inverse, st);
+    case tsdgpu_fft::EVEN: return step_even(p, x, y, batch, forward, st);
+    case tsdgpu_fft::ODD: return step_odd(p, x, y, batch, inverse, st);
   }
   return TSDGPU_OK;
+}
+
+// the transform of `batch` real vectors on device pointers (dx: n floats each, dy: n complex each)
+int rfft_device(tsdgpu_rfft *p, const void *dx, void *dy, int batch, hipStream_t st)
+{
+  const int n = p->n;
+  int rc = TSDGPU_OK;
+  if ((n & 1) == 0 && p->sub->kind == tsdgpu_fft::POW2_S16 && dev_switch("RFFT_TWO_PASS") == nullptr) {
+    // half-size Stockham transform with the untangling fused into its store: one pass over HBM
+    const int h = n / 2, tpt = h / 16, threads = std::max(256, tpt), T = threads / tpt;
+    const size_t lds = (size_t) T * (h + h / 16) * sizeof(cpx);
+    const unsigned grid = (unsigned) cdiv(batch, T);
+    const float scale = 1.0f / std::sqrt((float) h);
+    s16_radix(first_radix(p->sub->logn), [&](auto r) {
+      hipLaunchKernelGGL((fft_s16_kernel<decltype(r)::value>), dim3(grid), dim3(threads), lds, st, (const cpx *) dx, (cpx *) dy, p->sub->d_tw, h, tpt, 0,
+                         scale, batch, (const cpx *) p->d_rot);
+    });
+    TSD_HIP(hipGetLastError());
+  } else if ((n & 1) == 0) {
+    const int h = n / 2;
+    rc = p->work.reserve((size_t) h * batch * sizeof(cpx));
+    if (rc) return rc;
+    cpx *xt = p->work.as<cpx>();
+    rc = step_device(p->sub, (const cpx *) dx, xt, batch, 1, st);     // the real pairs, read as complex
+    if (rc) return rc;
+    const int64_t total = (int64_t) batch * (h + 1);
+    hipLaunchKernelGGL(rfft_untangle_kernel, dim3((unsigned) cdiv(total, 256)), dim3(256), 0, st, xt, (cpx *) dy, p->d_rot, n,
+                       total);
+    TSD_HIP(hipGetLastError());
+  } else {
+    // odd n: the reference simply transforms x.as_complex() (fourier.cc:348-352)
+    const int64_t total = (int64_t) batch * n;
+    hipLaunchKernelGGL(real_to_complex_kernel, dim3((unsigned) cdiv(total, 256)), dim3(256), 0, st, (const float *) dx,
+                       (cpx *) dy, total);
+    TSD_HIP(hipGetLastError());
+    rc = step_device(p->sub, (const cpx *) dy, (cpx *) dy, batch, 1, st);
+    if (rc) return rc;
+  }
+  return TSDGPU_OK;
+}
+
+// The step of a plan (tsdgpu_fft, tsdgpu_rfft) on host or device vectors of `batch` transforms, ESZ_IN bytes per input element
+// and ESZ_OUT per output element; SAME_OK: y may be x.  `device`(p, dx, dy, batch, stream) is the step on device pointers.
+template <size_t ESZ_IN, size_t ESZ_OUT, bool SAME_OK, typename PLAN, typename DEVICE>
+int plan_step(PLAN *p, const char *who, const void *x, void *y, int batch, hipStream_t st, DEVICE device)
+{
+  TSD_CHECK(p != nullptr, "%s: NULL plan", who);
+  TSD_CHECK(batch >= 0, "%s: negative batch", who);
+  if (batch == 0) return TSDGPU_OK;
+  if (SAME_OK) TSD_CHECK(x != nullptr && y != nullptr, "%s: NULL buffer", who);
+  else TSD_CHECK(x != nullptr && y != nullptr && x != y, "%s: needs distinct non-NULL buffers", who);
+  const int n = p->n;
+  const size_t in_bytes = (size_t) n * batch * ESZ_IN, out_bytes = (size_t) n * batch * ESZ_OUT;
+  const void *dx = nullptr;
+  void *dy = nullptr;
+  bool staged = false;
+  std::lock_guard<std::mutex> lock(p->order.mu);
+  int rc = p->order.enter(st);
+  if (rc) return rc;
+  // a large batch on HOST vectors goes through in chunks of whole transforms: H2D of chunk i + 1, the transforms of chunk i
+  // and D2H of chunk i - 1 overlap (common.hpp: pipelined_host_step_var)
+  if (batch >= 2 && out_bytes >= PIPE_MIN_BYTES && host_pipe_enabled() && !is_device_ptr(x) && !is_device_ptr(y) &&
+      ((SAME_OK && x == y) || !host_ranges_overlap(x, in_bytes, y, out_bytes))) {
+    rc = pipelined_host_step_var(
+        x, (int64_t) n * batch, ESZ_IN, y, ESZ_OUT, nullptr, n, st, [](int64_t c) { return c; },
+        [p, n, device](const void *cx, void *cy, int64_t cnt, int64_t, int64_t *got, hipStream_t q) {
+          *got = cnt;
+          return device(p, cx, cy, (int) (cnt / n), q);
+        });
+    if (rc) return rc;
+    return p->order.leave(st);
+  }
+  rc = stage_in(x, in_bytes, p->in_stage, st, &dx);
+  if (rc) return rc;
+  rc = stage_out(y, out_bytes, p->out_stage, &dy, &staged);
+  if (rc) return rc;
+  rc = device(p, dx, dy, batch, st);
+  if (rc) return rc;
+  rc = finish_out(y, out_bytes, dy, staged, st);
+  if (rc) return rc;
+  return p->order.leave(st);
 }
 
 }  // namespace
@@ -2937,41 +2989,10 @@ int tsdgpu_fft_create(tsdgpu_fft **out, int n, int batch_hint)
 
 int tsdgpu_fft_step(tsdgpu_fft *p, const void *x, void *y, int batch, int forward, void *stream)
 {
-  TSD_CHECK(p != nullptr, "fft_step: NULL plan");
-  TSD_CHECK(batch >= 0, "fft_step: negative batch");
-  if (batch == 0) return TSDGPU_OK;
-  TSD_CHECK(x != nullptr && y != nullptr, "fft_step: NULL buffer");
-  hipStream_t st = (hipStream_t) stream;
-  const size_t bytes = (size_t) p->n * batch * sizeof(cpx);
-  const void *dx = nullptr;
-  void *dy = nullptr;
-  bool staged = false;
-  std::lock_guard<std::mutex> lock(p->order.mu);
-  int rc = p->order.enter(st);
-  if (rc) return rc;
-  // a large batch on HOST vectors goes through in chunks of whole transforms: H2D of chunk i + 1, the transforms of chunk i
-  // and D2H of chunk i - 1 overlap (common.hpp: pipelined_host_step_var); y may be x
-  if (batch >= 2 && bytes >= PIPE_MIN_BYTES && host_pipe_enabled() && !is_device_ptr(x) && !is_device_ptr(y) &&
-      (x == y || !host_ranges_overlap(x, bytes, y, bytes))) {
-    const int n = p->n;
-    rc = pipelined_host_step_var(
-        x, (int64_t) n * batch, sizeof(cpx), y, sizeof(cpx), nullptr, n, st, [](int64_t c) { return c; },
-        [p, n, forward](const void *cx, void *cy, int64_t cnt, int64_t, int64_t *got, hipStream_t q) {
-          *got = cnt;
-          return step_device(p, (const cpx *) cx, (cpx *) cy, (int) (cnt / n), forward, q);
-        });
-    if (rc) return rc;
-    return p->order.leave(st);
-  }
-  rc = stage_in(x, bytes, p->in_stage, st, &dx);
-  if (rc) return rc;
-  rc = stage_out(y, bytes, p->out_stage, &dy, &staged);
-  if (rc) return rc;
-  rc = step_device(p, (const cpx *) dx, (cpx *) dy, batch, forward, st);
-  if (rc) return rc;
-  rc = finish_out(y, bytes, dy, staged, st);
-  if (rc) return rc;
-  return p->order.leave(st);
+  return plan_step<sizeof(cpx), sizeof(cpx), true>(p, "fft_step", x, y, batch, (hipStream_t) stream,
+                                                   [forward](tsdgpu_fft *q, const void *dx, void *dy, int b, hipStream_t st) {
+                                                     return step_device(q, (const cpx *) dx, (cpx *) dy, b, forward, st);
+                                                   });
 }
 
 int tsdgpu_fft_size(const tsdgpu_fft *p) { return p ? p->n : -1; }
@@ -3012,15 +3033,6 @@ int tsdgpu_fftshift(const void *x, void *y, int n, int data_type, void *stream)
   return rc;
 }
 
-/* ---- real FFT ---------------------------------------------------------------------------- */
-struct tsdgpu_rfft {
-  int n = 0;
-  tsdgpu_fft *sub = nullptr;      // n/2-point complex plan (even n) or n-point plan (odd n)
-  cpx *d_rot = nullptr;           // tfr_rotation(n): W_n^i, double recurrence rounded to float
-  DevBuf work, in_stage, out_stage;
-  StepOrder order;
-};
-
 int tsdgpu_rfft_create(tsdgpu_rfft **out, int n)
 {
   TSD_CHECK(out != nullptr, "rfft_create: out is NULL");
@@ -3031,18 +3043,7 @@ int tsdgpu_rfft_create(tsdgpu_rfft **out, int n)
   int rc = TSDGPU_OK;
   if ((n & 1) == 0) {
     rc = plan_create(&p->sub, n / 2);
-    if (!rc) {
-      std::vector<cpx> rot((size_t) n);
-      const double PI = 3.14159265358979323846;
-      double rr = 1.0, ri = 0.0;
-      const double wr = std::cos(-2 * PI / n), wi = std::sin(-2 * PI / n);
-      for (int i = 0; i < n; i++) {
-        rot[i] = make_float2((float) rr, (float) ri);
-        const double tr = rr * wr - ri * wi, ti = rr * wi + ri * wr;
-        rr = tr; ri = ti;
-      }
-      rc = upload(&p->d_rot, rot);
-    }
+    if (!rc) rc = upload(&p->d_rot, rotation_table(n));
   } else {
     rc = plan_create(&p->sub, n);
   }
@@ -3054,83 +3055,9 @@ int tsdgpu_rfft_create(tsdgpu_rfft **out, int n)
   return TSDGPU_OK;
 }
 
-}  // extern "C"
-// the transform of `batch` real vectors on device pointers (dx: n floats each, dy: n complex each)
-static int rfft_device(tsdgpu_rfft *p, const void *dx, void *dy, int batch, hipStream_t st)
-{
-  const int n = p->n;
-  int rc = TSDGPU_OK;
-  if ((n & 1) == 0 && p->sub->kind == tsdgpu_fft::POW2_S16 && dev_switch("RFFT_TWO_PASS") == nullptr) {
-    // half-size Stockham transform with the untangling fused into its store: one pass over HBM
-    const int h = n / 2, tpt = h / 16, threads = std::max(256, tpt), T = threads / tpt;
-    const size_t lds = (size_t) T * (h + h / 16) * sizeof(cpx);
-    const unsigned grid = (unsigned) cdiv(batch, T);
-    const int r0 = 1 << ((p->sub->logn & 3) == 0 ? 4 : (p->sub->logn & 3));
-    const float scale = 1.0f / std::sqrt((float) h);
-#define S16R_LAUNCH(R) hipLaunchKernelGGL((fft_s16_kernel<R>), dim3(grid), dim3(threads), lds, st, (const cpx *) dx, (cpx *) dy, p->sub->d_tw, h, tpt, 0, scale, batch, (const cpx *) p->d_rot)
-    if (r0 == 16) S16R_LAUNCH(16); else if (r0 == 8) S16R_LAUNCH(8); else if (r0 == 4) S16R_LAUNCH(4); else S16R_LAUNCH(2);
-#undef S16R_LAUNCH
-    TSD_HIP(hipGetLastError());
-  } else if ((n & 1) == 0) {
-    const int h = n / 2;
-    rc = p->work.reserve((size_t) h * batch * sizeof(cpx));
-    if (rc) return rc;
-    cpx *xt = p->work.as<cpx>();
-    rc = step_device(p->sub, (const cpx *) dx, xt, batch, 1, st);     // the real pairs, read as complex
-    if (rc) return rc;
-    const int64_t total = (int64_t) batch * (h + 1);
-    hipLaunchKernelGGL(rfft_untangle_kernel, dim3((unsigned) cdiv(total, 256)), dim3(256), 0, st, xt, (cpx *) dy, p->d_rot, n,
-                       total);
-    TSD_HIP(hipGetLastError());
-  } else {
-    // odd n: the reference simply transforms x.as_complex() (fourier.cc:348-352)
-    const int64_t total = (int64_t) batch * n;
-    hipLaunchKernelGGL(real_to_complex_kernel, dim3((unsigned) cdiv(total, 256)), dim3(256), 0, st, (const float *) dx,
-                       (cpx *) dy, total);
-    TSD_HIP(hipGetLastError());
-    rc = step_device(p->sub, (const cpx *) dy, (cpx *) dy, batch, 1, st);
-    if (rc) return rc;
-  }
-  return TSDGPU_OK;
-}
-extern "C" {
-
 int tsdgpu_rfft_step(tsdgpu_rfft *p, const void *x, void *y, int batch, void *stream)
 {
-  TSD_CHECK(p != nullptr, "rfft_step: NULL plan");
-  TSD_CHECK(batch >= 0, "rfft_step: negative batch");
-  if (batch == 0) return TSDGPU_OK;
-  TSD_CHECK(x != nullptr && y != nullptr && x != y, "rfft_step: needs distinct non-NULL buffers");
-  hipStream_t st = (hipStream_t) stream;
-  const int n = p->n;
-  const size_t in_bytes = (size_t) n * batch * sizeof(float), out_bytes = (size_t) n * batch * sizeof(cpx);
-  const void *dx = nullptr;
-  void *dy = nullptr;
-  bool staged = false;
-  std::lock_guard<std::mutex> lock(p->order.mu);
-  int rc = p->order.enter(st);
-  if (rc) return rc;
-  // a large batch on HOST vectors: chunks of whole transforms through the staging pipeline (see tsdgpu_fft_step)
-  if (batch >= 2 && out_bytes >= PIPE_MIN_BYTES && host_pipe_enabled() && !is_device_ptr(x) && !is_device_ptr(y) &&
-      !host_ranges_overlap(x, in_bytes, y, out_bytes)) {
-    rc = pipelined_host_step_var(
-        x, (int64_t) n * batch, sizeof(float), y, sizeof(cpx), nullptr, n, st, [](int64_t c) { return c; },
-        [p, n](const void *cx, void *cy, int64_t cnt, int64_t, int64_t *got, hipStream_t q) {
-          *got = cnt;
-          return rfft_device(p, cx, cy, (int) (cnt / n), q);
-        });
-    if (rc) return rc;
-    return p->order.leave(st);
-  }
-  rc = stage_in(x, in_bytes, p->in_stage, st, &dx);
-  if (rc) return rc;
-  rc = stage_out(y, out_bytes, p->out_stage, &dy, &staged);
-  if (rc) return rc;
-  rc = rfft_device(p, dx, dy, batch, st);
-  if (rc) return rc;
-  rc = finish_out(y, out_bytes, dy, staged, st);
-  if (rc) return rc;
-  return p->order.leave(st);
+  return plan_step<sizeof(float), sizeof(cpx), false>(p, "rfft_step", x, y, batch, (hipStream_t) stream, rfft_device);
 }
 
 int tsdgpu_rfft_destroy(tsdgpu_rfft *p)

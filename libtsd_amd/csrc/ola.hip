@@ -141,16 +141,13 @@ bool framed_fft_launch(const tsdgpu_fft *plan, const FrameSrc &S, int64_t nfr, c
   const size_t lds = (size_t) T * (N + N / 16) * sizeof(cpx);
   int logn = 0;
   while ((1 << logn) < N) logn++;
-  const int r0 = 1 << ((logn & 3) == 0 ? 4 : (logn & 3));
   const float scale = 1.0f / std::sqrt((float) N);
   const unsigned grid = (unsigned) cdiv(nfr, T);
-#define FR_LAUNCH(R)                                                                                                      \
-  do {                                                                                                                    \
-    (void) hipFuncSetAttribute((const void *) framed_fft_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((framed_fft_kernel<R>), dim3(grid), dim3(threads), lds, st, S, TW, tpt, scale, nfr, H, outc, outp);  \
-  } while (0)
-  if (r0 == 16) FR_LAUNCH(16); else if (r0 == 8) FR_LAUNCH(8); else if (r0 == 4) FR_LAUNCH(4); else FR_LAUNCH(2);
-#undef FR_LAUNCH
+  s16_radix(first_radix(logn), [&](auto r) {
+    constexpr int R = decltype(r)::value;
+    (void) hipFuncSetAttribute((const void *) framed_fft_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((framed_fft_kernel<R>), dim3(grid), dim3(threads), lds, st, S, TW, tpt, scale, nfr, H, outc, outp);
+  });
   return true;
 }
 
@@ -289,7 +286,7 @@ int ola_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx *
   const int tpt = g.tpt, T = g.T;
   int logn = 0;
   while ((1 << logn) < N) logn++;
-  const int r0 = 1 << ((logn & 3) == 0 ? 4 : (logn & 3));
+  const int r0 = first_radix(logn);
   // blocks per run: every run recomputes the block before it, so a run costs per + 1 blocks, and the workgroups pass over
   // the chip in rounds of (CUs x resident workgroups): the cheapest (rounds x (per + 1)) wins
   static const int cus = []() {
@@ -306,23 +303,20 @@ int ola_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx *
   }
   const int64_t runs = cdiv(B, per), grid = cdiv(runs, T);
   if (grid > 0x7fffffff) return set_err(TSDGPU_ERR_UNSUPPORTED, "ola: too many blocks in one call");
-#define RUN_LAUNCH(R, TH, HF)                                                                                            \
-  do {                                                                                                                   \
-    (void) hipFuncSetAttribute((const void *) ola_run_kernel<R, TH, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((ola_run_kernel<R, TH, HF>), dim3((unsigned) grid), dim3(TH), g.lds, st, blk0, nrest, x, y, tables, tables + N, svg_in, svg_out, Ne, N, tpt, B, per); \
-  } while (0)
-#define RUN_PICK(TH, HF)                                                                                                 \
-  do {                                                                                                                   \
-    if (r0 == 16) RUN_LAUNCH(16, TH, HF); else if (r0 == 8) RUN_LAUNCH(8, TH, HF); else if (r0 == 4) RUN_LAUNCH(4, TH, HF); else RUN_LAUNCH(2, TH, HF); \
-  } while (0)
-  if (g.threads == 256 && g.half) RUN_PICK(256, true);
-  else if (g.threads == 256) RUN_PICK(256, false);
-  else if (g.threads == 512 && g.half) RUN_PICK(512, true);
-  else if (g.threads == 512) RUN_PICK(512, false);
-  else if (g.threads == 1024 && g.half) RUN_PICK(1024, true);
+  auto pick = [&](auto th, auto hf) {
+    s16_radix(r0, [&](auto r) {
+      constexpr int R = decltype(r)::value, TH = decltype(th)::value;
+      constexpr bool HF = decltype(hf)::value;
+      (void) hipFuncSetAttribute((const void *) ola_run_kernel<R, TH, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL((ola_run_kernel<R, TH, HF>), dim3((unsigned) grid), dim3(TH), g.lds, st, blk0, nrest, x, y, tables, tables + N, svg_in, svg_out, Ne, N, tpt, B, per);
+    });
+  };
+  if (g.threads == 256 && g.half) pick(int_c<256>(), std::true_type());
+  else if (g.threads == 256) pick(int_c<256>(), std::false_type());
+  else if (g.threads == 512 && g.half) pick(int_c<512>(), std::true_type());
+  else if (g.threads == 512) pick(int_c<512>(), std::false_type());
+  else if (g.threads == 1024 && g.half) pick(int_c<1024>(), std::true_type());
   else return set_err(TSDGPU_ERR_UNSUPPORTED, "ola: frame of %d points does not fit the fused kernel", N);   // (set_response does not select it)
-#undef RUN_PICK
-#undef RUN_LAUNCH
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
@@ -491,7 +485,7 @@ int olaw_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx 
   const OlawGeom g = olaw_geom(N, Ne);
   int logn = 0;
   while ((1 << logn) < N) logn++;
-  const int r0 = 1 << ((logn & 3) == 0 ? 4 : (logn & 3));
+  const int r0 = first_radix(logn);
   static const int cus = []() {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
@@ -507,19 +501,12 @@ int olaw_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx 
   }
   const int64_t grid = cdiv(cdiv(B, per), g.T);
   if (grid > 0x7fffffff) return set_err(TSDGPU_ERR_UNSUPPORTED, "ola: too many blocks in one call");
-#define RUNW_LAUNCH(R, TH)                                                                                                \
-  do {                                                                                                                   \
-    (void) hipFuncSetAttribute((const void *) olaw_run_kernel<R, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((olaw_run_kernel<R, TH>), dim3((unsigned) grid), dim3(TH), g.lds, st, blk0, nrest, x, y, tables, tables + N, fen, svg_in, last_in, prev_half_in, svg_out, last_out, Ne, N, g.tpt, B, per, skip_first); \
-  } while (0)
-#define RUNW_PICK(TH)                                                                                                    \
-  do {                                                                                                                   \
-    if (r0 == 16) RUNW_LAUNCH(16, TH); else if (r0 == 8) RUNW_LAUNCH(8, TH); else if (r0 == 4) RUNW_LAUNCH(4, TH); else RUNW_LAUNCH(2, TH); \
-  } while (0)
-  if (g.threads == 64) RUNW_PICK(64);
-  else return set_err(TSDGPU_ERR_UNSUPPORTED, "ola: frame of %d points does not fit the fused windowed kernel", N);
-#undef RUNW_PICK
-#undef RUNW_LAUNCH
+  if (g.threads != 64) return set_err(TSDGPU_ERR_UNSUPPORTED, "ola: frame of %d points does not fit the fused windowed kernel", N);
+  s16_radix(r0, [&](auto r) {
+    constexpr int R = decltype(r)::value, TH = 64;
+    (void) hipFuncSetAttribute((const void *) olaw_run_kernel<R, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((olaw_run_kernel<R, TH>), dim3((unsigned) grid), dim3(TH), g.lds, st, blk0, nrest, x, y, tables, tables + N, fen, svg_in, last_in, prev_half_in, svg_out, last_out, Ne, N, g.tpt, B, per, skip_first);
+  });
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }
@@ -617,23 +604,17 @@ int seg_runs_launch(const cpx *x, const float *w, const cpx *TW, float *part, in
   const OlaRunGeom g = ola_run_geom(N, N / 2);
   int logn = 0;
   while ((1 << logn) < N) logn++;
-  const int r0 = 1 << ((logn & 3) == 0 ? 4 : (logn & 3));
+  const int r0 = first_radix(logn);
   const int64_t grid = cdiv(nruns, g.T);
-#define WR_LAUNCH(R, TH)                                                                                                 \
-  do {                                                                                                                   \
-    (void) hipFuncSetAttribute((const void *) welch_run_kernel<R, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipLaunchKernelGGL((welch_run_kernel<R, TH>), dim3((unsigned) grid), dim3(TH), g.lds, st, x, w, TW, part, N, g.tpt, M, nruns); \
-  } while (0)
-#define WR_PICK(TH)                                                                                                      \
-  do {                                                                                                                   \
-    if (r0 == 16) WR_LAUNCH(16, TH); else if (r0 == 8) WR_LAUNCH(8, TH); else if (r0 == 4) WR_LAUNCH(4, TH); else WR_LAUNCH(2, TH); \
-  } while (0)
-  if (g.threads == 256) WR_PICK(256);
-  else if (g.threads == 512) WR_PICK(512);
-  else if (g.threads == 1024) WR_PICK(1024);
-  else return set_err(TSDGPU_ERR_UNSUPPORTED, "welch: N = %d does not fit the fused kernel", N);
-#undef WR_PICK
-#undef WR_LAUNCH
+  if (g.threads != 256 && g.threads != 512 && g.threads != 1024)
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "welch: N = %d does not fit the fused kernel", N);
+  int_switch<256, 512, 1024>(g.threads, [&](auto th) {
+    s16_radix(r0, [&](auto r) {
+      constexpr int R = decltype(r)::value, TH = decltype(th)::value;
+      (void) hipFuncSetAttribute((const void *) welch_run_kernel<R, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipLaunchKernelGGL((welch_run_kernel<R, TH>), dim3((unsigned) grid), dim3(TH), g.lds, st, x, w, TW, part, N, g.tpt, M, nruns);
+    });
+  });
   TSD_HIP(hipGetLastError());
   return TSDGPU_OK;
 }

@@ -147,21 +147,16 @@ int ols_long_step(tsdgpu_fir *f, const void *x, void *y, int64_t n, hipStream_t 
   const int N = f->ols_N, L = f->ols_L, tpt = N / 16;
   int logn = 0;
   while ((1 << logn) < N) logn++;
-  const int r0 = 1 << ((logn & 3) == 0 ? 4 : (logn & 3));
   const bool real = f->data_type == TSDGPU_F32;
   const int64_t nblocks = cdiv(n, real ? 2 * (int64_t) L : L);      // real data: one workgroup per pair of blocks
   TSD_CHECK(nblocks <= 0x7fffffff, "fir_step: too many blocks");
   const size_t lds = (size_t) (N + N / 16) * sizeof(cpx);
   const cpx *H = (const cpx *) f->d_H, *TW = H + N;
-#define OLSL_LAUNCH(R, B)                                                                                         \
-  hipLaunchKernelGGL((ols_long_kernel<R, B>), dim3((unsigned) nblocks), dim3(tpt), lds, st, x, (const void *) fir_hist_read(f), \
-                     y, H, TW, N, tpt, f->K, f->HL, L, n)
-  if (real) {
-    if (r0 == 16) OLSL_LAUNCH(16, true); else if (r0 == 8) OLSL_LAUNCH(8, true); else if (r0 == 4) OLSL_LAUNCH(4, true); else OLSL_LAUNCH(2, true);
-  } else {
-    if (r0 == 16) OLSL_LAUNCH(16, false); else if (r0 == 8) OLSL_LAUNCH(8, false); else if (r0 == 4) OLSL_LAUNCH(4, false); else OLSL_LAUNCH(2, false);
-  }
-#undef OLSL_LAUNCH
+  s16_radix(first_radix(logn), [&](auto r) {
+    constexpr int R = decltype(r)::value;
+    auto *kernel = real ? ols_long_kernel<R, true> : ols_long_kernel<R, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned) nblocks), dim3(tpt), lds, st, x, (const void *) fir_hist_read(f), y, H, TW, N, tpt, f->K, f->HL, L, n);
+  });
   TSD_HIP(hipGetLastError());
   return fir_update_history(f, x, n, st);
 }

@@ -249,9 +249,7 @@ int polybank_launch(PolyBank *c, const char *op, void (*kernel)(KA...), const Po
   return TSDGPU_OK;
 }
 
-// The maps to a kernel's template arguments, as std::integral_constants: compile-time switches, nothing looked up or allocated
-// on the way to a launch.
-template <int V> using int_c = std::integral_constant<int, V>;
+// The maps to a kernel's template arguments, as int_c of common.hpp.
 constexpr int POLYBANK_UNSERVED = -1;   // no case below: the caller words the refusal (not a status of tsdgpu.h)
 
 // fn(R0, NPOS): R0 the first radix of the T-point transform (0: T = 8), NPOS = 2 at T = 1024
