@@ -485,6 +485,16 @@ bool host_ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
   return pa < pb + nb && pb < pa + na;
 }
 
+int cu_count()
+{
+  static const int NCU = [] {
+    int dev = 0, c = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+    return c > 0 ? c : 256;
+  }();
+  return NCU;
+}
+
 }  // namespace tsdgpu
 
 extern "C" {

@@ -160,6 +160,8 @@ int fft_blu_framed_launch(const tsdgpu_fft *p, const float2 *x, int64_t pas, con
                           int64_t *rows, void *stream);
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// compute units of the current device, asked once per process (the devices of a node are alike); 256 when the query fails
+int cu_count();
 
 // The maps from a run-time value to a kernel's template argument, as std::integral_constants: compile-time switches, nothing
 // looked up or allocated on the way to a launch.  int_switch<A, B, ..., Z>(v, fn) calls the generic lambda fn with int_c<A>() where

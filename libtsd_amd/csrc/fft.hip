@@ -1997,16 +1997,6 @@ template <int BYTES = 160 * 1024, typename... K> void raise_lds(K... kernels)
   ((void) hipFuncSetAttribute((const void *) kernels, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES), ...);
 }
 
-int cu_count()
-{
-  static const int NCU = [] {
-    int dev = 0, c = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return c > 0 ? c : 256;
-  }();
-  return NCU;
-}
-
 int upload(cpx **dst, const std::vector<cpx> &v)
 {
   if (hipMalloc((void **) dst, v.size() * sizeof(cpx)) != hipSuccess)

@@ -289,12 +289,7 @@ int ola_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx *
   const int r0 = first_radix(logn);
   // blocks per run: every run recomputes the block before it, so a run costs per + 1 blocks, and the workgroups pass over
   // the chip in rounds of (CUs x resident workgroups): the cheapest (rounds x (per + 1)) wins
-  static const int cus = []() {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const int64_t slots = (int64_t) cus * std::max<int64_t>(1, std::min<int64_t>(g.threads == 256 ? 3 : 1, (int64_t) ((160 * 1024) / g.lds)));   // (registers: 3 waves per SIMD)
+  const int64_t slots = (int64_t) cu_count() * std::max<int64_t>(1, std::min<int64_t>(g.threads == 256 ? 3 : 1, (int64_t) ((160 * 1024) / g.lds)));   // (registers: 3 waves per SIMD)
   int per = 1;
   int64_t best = -1;
   for (int c = 1; c <= 32; c++) {
@@ -486,13 +481,8 @@ int olaw_run_launch(const cpx *blk0, int nrest, const cpx *x, cpx *y, const cpx 
   int logn = 0;
   while ((1 << logn) < N) logn++;
   const int r0 = first_radix(logn);
-  static const int cus = []() {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
   // blocks per run: a run costs per + 1.5 blocks (its warm-up), the workgroups pass over the chip in rounds
-  const int64_t slots = (int64_t) cus * std::max<int64_t>(1, std::min<int64_t>(g.threads == 64 ? 16 : g.threads == 256 ? 2 : 1, (int64_t) ((160 * 1024) / g.lds)));
+  const int64_t slots = (int64_t) cu_count() * std::max<int64_t>(1, std::min<int64_t>(g.threads == 64 ? 16 : g.threads == 256 ? 2 : 1, (int64_t) ((160 * 1024) / g.lds)));
   int per = 1;
   int64_t best = -1;
   for (int c = 1; c <= 64; c++) {
@@ -890,6 +880,131 @@ int ola_alloc(cpx **p, size_t count)
   return TSDGPU_OK;
 }
 
+// dst[i] = W_N^i, i < N/16: the twiddles the Stockham transform takes from a table (stockham16.hpp), in double, rounded once
+void fill_w16(cpx *dst, int N)
+{
+  const double PI = 3.14159265358979323846;
+  for (int i = 0; i < N / 16; i++) {
+    const double a = -2.0 * PI * (double) i / (double) N;
+    dst[i] = make_float2((float) std::cos(a), (float) std::sin(a));
+  }
+}
+
+// tsdgpu_ola_step once a response is set and its geometry has a fused kernel (d_run): the B >= 1 whole blocks of [rest ++ x]
+// through ONE kernel, 16 B of HBM traffic per sample.  Which kernel is the only thing the geometries differ in:
+//   no window, Ne = 512, N = 1024, nothing waiting    ola1024_kernel (ols.hip), in-wave
+//   no window, anything else                          ola_run_kernel
+//   window, Ne = N = 512                              olaw512_kernel (ols.hip), in-wave pair transform
+//   window, anything else                             olaw_run_kernel
+// nrest, cnt_ech and *n_out are committed once the last launch has been accepted.
+int ola_fused_step(tsdgpu_ola *h, const void *x, int64_t n, void *y, int64_t *n_out, hipStream_t st)
+{
+  const int Ne = h->Ne, nrest = h->nrest;
+  const int64_t tot = (int64_t) nrest + n, B = tot / Ne, left = tot - B * Ne;
+  const int skip = h->windowed && h->cnt_ech < 0 ? 1 : 0;        // (:899-901: the very first windowed block gives no output)
+  const int64_t nout = (B - skip) * Ne;
+  const bool in_wave = h->d_fast && !h->windowed && nrest == 0;
+  if (n_out) *n_out = 0;
+  TSD_CHECK(in_wave || B <= (1 << 24), "ola_step: %lld blocks in one call", (long long) B);
+  const void *dxv = nullptr;
+  void *dyv = nullptr;
+  bool staged = false;
+  int rc = stage_in(x, (size_t) n * sizeof(cpx), h->in_stage, st, &dxv);
+  if (rc) return rc;
+  if ((rc = stage_out(y, (size_t) nout * sizeof(cpx), h->out_stage, &dyv, &staged))) return rc;
+  if (nout > 0 && host_ranges_overlap(dxv, (size_t) n * sizeof(cpx), dyv, (size_t) nout * sizeof(cpx))) {
+    // y on x, wholly or in part: a run re-reads the blocks before it, which the run before may already have overwritten
+    if ((rc = h->in_stage.reserve((size_t) n * sizeof(cpx)))) return rc;
+    TSD_HIP(hipMemcpyAsync(h->in_stage.p, dxv, (size_t) n * sizeof(cpx), hipMemcpyDeviceToDevice, st));
+    dxv = h->in_stage.p;
+  }
+  const cpx *dx = (const cpx *) dxv;
+  cpx *dy = (cpx *) dyv;
+  // block 0 made contiguous: the waiting samples, then the head of x (rest has room for a whole block)
+  if (nrest > 0 && (rc = copy_small(h->d_rest + nrest, dx, Ne - nrest, st))) return rc;
+  const cpx *blk0 = nrest > 0 ? h->d_rest : dx;
+  if (in_wave)
+    rc = ola1024_launch(dx, dy, h->d_fast, h->d_svg, h->d_svg_tmp, B, st);
+  else if (!h->windowed)
+    rc = ola_run_launch(blk0, nrest, dx, dy, h->d_run, h->d_svg, h->d_svg_tmp, Ne, h->N, B, st);
+  else if (h->d_fast && h->N == 512 && Ne == 512)
+    rc = olaw512_launch(blk0, nrest, dx, dy, h->d_fast, h->d_fen, h->d_svg, h->d_last, h->d_prev_half, h->d_svg_tmp, h->d_last_tmp, B, skip, st);
+  else
+    rc = olaw_run_launch(blk0, nrest, dx, dy, h->d_run, h->d_fen, h->d_svg, h->d_last, h->d_prev_half, h->d_svg_tmp, h->d_last_tmp, Ne, h->N, B, skip, st);
+  if (rc) return rc;
+  std::swap(h->d_svg, h->d_svg_tmp);              // (the last run wrote the new tail beside the one the first run read)
+  if (h->windowed) {
+    std::swap(h->d_last, h->d_last_tmp);
+    // the second half of the last block waits for the next call's first frame (:926)
+    hipLaunchKernelGGL(ola_gather_kernel, dim3(nblk(Ne / 2)), dim3(256), 0, st, h->d_rest, nrest, dx, (B - 1) * Ne + Ne / 2, h->d_prev_half, Ne / 2);
+    TSD_HIP(hipGetLastError());
+  }
+  // the samples after the last whole block lie inside x (B >= 1): rest is only written
+  if ((rc = copy_small(h->d_rest, dx + (B * Ne - nrest), left, st))) return rc;
+  if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
+  if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
+  h->nrest = (int) left;
+  h->cnt_ech += B * Ne;
+  if (n_out) *n_out = nout;
+  return TSDGPU_OK;
+}
+
+// ---- psd_welch: what a call borrows, and the reduction its three fused producers share ------------------------------
+// scratch and plan borrowed for the call (the one-shot API used to spend most of its time in hipMalloc / hipFree and in
+// building the plan)
+struct WelchCtx {
+  int dev = 0, N = 0, lots = 0;
+  tsdgpu_fft *plan = nullptr;
+  DevBuf xin, seg, part, wbuf, sout, tw;
+  int tw_N = 0;                     // the size the transform tables in tw were made for (0: none)
+  void libere() { if (plan) tsdgpu_fft_destroy(plan); xin.release(); seg.release(); part.release(); wbuf.release(); sout.release(); tw.release(); }
+  size_t octets() const { return xin.cap + seg.cap + part.cap + wbuf.cap + sout.cap; }
+};
+
+// the tables of the fused transform of N points in c->tw: the in-wave kernel's at N = 1024 (ols.hip), else W_N^i
+int welch_tables(WelchCtx *c, int N)
+{
+  if (c->tw_N == N) return TSDGPU_OK;
+  std::vector<cpx> t(N == 1024 ? 2048 : (size_t) N / 16);
+  if (N == 1024) welch1024_tables(t.data());
+  else fill_w16(t.data(), N);
+  c->tw_N = 0;
+  int rc = c->tw.reserve(t.size() * sizeof(cpx));
+  if (!rc && hipMemcpy(c->tw.p, t.data(), t.size() * sizeof(cpx), hipMemcpyHostToDevice) != hipSuccess)
+    rc = set_err(TSDGPU_ERR_HIP, "welch: table upload failed");
+  if (!rc) c->tw_N = N;
+  return rc;
+}
+
+// The partial rows of a producer (one per run, wave or workgroup: hundreds to thousands) are summed in two deterministic
+// stages -- groups of rpg rows over many workgroups, then 4 row lanes per bin.  (A single stage would walk thousands of rows
+// from four workgroups; the 64-group form -- 35 rows per thread from 256 workgroups, then 64 rows per thread from four -- took
+// 27 + 16 us of a call's 118.)  part holds the producer's rows at p1 and the ngr group sums behind them at p2.
+struct WelchRows {
+  int rpg, ngr;
+  float *p1, *p2;
+};
+int welch_rows_layout(DevBuf &part, int64_t rows, int N, WelchRows *L)
+{
+  L->rpg = (int) std::min<int64_t>(64, std::max<int64_t>(8, cdiv(rows, 96)));
+  L->ngr = (int) cdiv(rows, L->rpg);
+  const int rc = part.reserve((size_t) (rows + L->ngr) * N * sizeof(float));
+  L->p1 = part.as<float>();
+  L->p2 = L->p1 + (size_t) rows * N;
+  return rc;
+}
+// S = the sum of the rows; shift: the rows are in transform order, S in fftshift order (0: the rows already are)
+int welch_reduce_rows(DevBuf &part, int64_t rows, int N, int shift, float *dS, hipStream_t st)
+{
+  WelchRows L;
+  const int rc = welch_rows_layout(part, rows, N, &L);          // (reserved by the producer's caller: nothing moves)
+  if (rc) return rc;
+  hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) L.ngr), dim3(256), 0, st, L.p1, L.p2, N, (int) rows, L.rpg);
+  hipLaunchKernelGGL(welch_sum_shift_kernel, dim3((unsigned) cdiv(N, 64)), dim3(256), 0, st, L.p2, dS, N, L.ngr, shift);
+  if (hipGetLastError() != hipSuccess) return set_err(TSDGPU_ERR_HIP, "welch: launch failed");
+  return TSDGPU_OK;
+}
+
 }  // namespace
 }  // namespace tsdgpu
 
@@ -950,46 +1065,40 @@ int tsdgpu_ola_set_response(tsdgpu_ola *h, const void *H)
 {
   TSD_CHECK(h != nullptr, "ola_set_response: NULL handle");
   if (!H) {
-    if (h->d_H) (void) hipFree(h->d_H);
-    h->d_H = nullptr;
-    if (h->d_fast) (void) hipFree(h->d_fast);
-    h->d_fast = nullptr;
-    if (h->d_run) (void) hipFree(h->d_run);
-    h->d_run = nullptr;
+    for (cpx **q : {&h->d_H, &h->d_fast, &h->d_run}) {
+      if (*q) (void) hipFree(*q);
+      *q = nullptr;
+    }
     return TSDGPU_OK;
   }
-  if (!h->d_H) TSD_HIP(hipMalloc((void **) &h->d_H, (size_t) h->N * sizeof(cpx)));
-  TSD_HIP(hipMemcpy(h->d_H, H, (size_t) h->N * sizeof(cpx), hipMemcpyDefault));
+  const int N = h->N;
+  if (!h->d_H) TSD_HIP(hipMalloc((void **) &h->d_H, (size_t) N * sizeof(cpx)));
+  TSD_HIP(hipMemcpy(h->d_H, H, (size_t) N * sizeof(cpx), hipMemcpyDefault));
+  // an in-wave kernel's image of the response (ols.hip), `count` values in d_fast
+  auto in_wave = [h, N](void (*tables)(const cpx *, cpx *), size_t count) -> int {
+    std::vector<cpx> Hh(N), tb(count);
+    TSD_HIP(hipMemcpy(Hh.data(), h->d_H, (size_t) N * sizeof(cpx), hipMemcpyDeviceToHost));
+    tables(Hh.data(), tb.data());
+    if (!h->d_fast) TSD_HIP(hipMalloc((void **) &h->d_fast, count * sizeof(cpx)));
+    TSD_HIP(hipMemcpy(h->d_fast, tb.data(), count * sizeof(cpx), hipMemcpyHostToDevice));
+    return TSDGPU_OK;
+  };
+  int rc = TSDGPU_OK;
   // the reference's default geometry without window: one fused kernel (ols.hip, ola1024_kernel) serves whole-block calls
   static const bool unfused = dev_switch("OLA_UNFUSED") != nullptr;
-  if (!unfused && !h->windowed && h->N == 1024 && h->Ne == 512) {
-    std::vector<cpx> Hh(1024), t3(3 * 1024);
-    TSD_HIP(hipMemcpy(Hh.data(), h->d_H, 1024 * sizeof(cpx), hipMemcpyDeviceToHost));
-    ola1024_tables(Hh.data(), t3.data());
-    if (!h->d_fast) TSD_HIP(hipMalloc((void **) &h->d_fast, t3.size() * sizeof(cpx)));
-    TSD_HIP(hipMemcpy(h->d_fast, t3.data(), t3.size() * sizeof(cpx), hipMemcpyHostToDevice));
-  }
+  if (!unfused && !h->windowed && N == 1024 && h->Ne == 512 && (rc = in_wave(ola1024_tables, 3 * 1024))) return rc;
   // the windowed mode at Ne = N = 512 (the engine's defaults with a window): the in-wave pair transform (ols.hip, olaw512_kernel)
   static const bool no_w512 = dev_switch("OLAW512") != nullptr && atoi(dev_switch("OLAW512")) == 0;
-  if (!unfused && !no_w512 && h->windowed && h->N == 512 && h->Ne == 512) {
-    std::vector<cpx> Hh(512), tb(512 + 2 * 1024);
-    TSD_HIP(hipMemcpy(Hh.data(), h->d_H, 512 * sizeof(cpx), hipMemcpyDeviceToHost));
-    olaw512_tables(Hh.data(), tb.data());
-    if (!h->d_fast) TSD_HIP(hipMalloc((void **) &h->d_fast, tb.size() * sizeof(cpx)));
-    TSD_HIP(hipMemcpy(h->d_fast, tb.data(), tb.size() * sizeof(cpx), hipMemcpyHostToDevice));
-  }
-  if (!unfused && (h->windowed ? olaw_run_fits(h->N, h->Ne) : ola_run_fits(h->N, h->Ne))) {
+  if (!unfused && !no_w512 && h->windowed && N == 512 && h->Ne == 512 && (rc = in_wave(olaw512_tables, 512 + 2 * 1024))) return rc;
+  if (!unfused && (h->windowed ? olaw_run_fits(N, h->Ne) : ola_run_fits(N, h->Ne))) {
     // the other geometries whose frame and carried block fit the LDS: one kernel too (ola_run_kernel) -- which also serves the
-    // ragged calls of the default geometry (waiting samples in front of x), the in-wave kernel taking the whole-block ones
-    const int N = h->N;
+    // ragged calls of the default geometry (waiting samples in front of x), the in-wave kernel taking the whole-block ones.
+    // Both in-wave geometries fit (34 KiB of LDS at 256 threads, 24.5 KiB at 64): a handle whose response was accepted never
+    // has d_fast without d_run, and d_run is what tsdgpu_ola_step asks for.
     std::vector<cpx> tb((size_t) N + N / 16);
     TSD_HIP(hipMemcpy(tb.data(), h->d_H, (size_t) N * sizeof(cpx), hipMemcpyDeviceToHost));
     for (int i = 0; i < N; i++) tb[i] = make_float2(tb[i].x / (float) N, tb[i].y / (float) N);
-    const double PI = 3.14159265358979323846;
-    for (int i = 0; i < N / 16; i++) {
-      const double a = -2.0 * PI * (double) i / (double) N;
-      tb[(size_t) N + i] = make_float2((float) std::cos(a), (float) std::sin(a));
-    }
+    fill_w16(tb.data() + N, N);
     if (!h->d_run) TSD_HIP(hipMalloc((void **) &h->d_run, tb.size() * sizeof(cpx)));
     TSD_HIP(hipMemcpy(h->d_run, tb.data(), tb.size() * sizeof(cpx), hipMemcpyHostToDevice));
   }
@@ -1039,15 +1148,9 @@ int tsdgpu_ola_analyse(tsdgpu_ola *h, const void *x, int64_t n, void **spectra, 
   }
   // the samples after the last whole block wait for the next call
   const int left = (int) (tot - B * Ne);
-  if (B > 0) {
-    if (left > 0) {
-      hipLaunchKernelGGL(ola_gather_kernel, dim3(nblk(left)), dim3(256), 0, st, h->d_rest, 0, dx, B * Ne - h->nrest, h->d_rest,
-                         left);                                    // lies inside x (B >= 1): rest is only written
-      TSD_HIP(hipGetLastError());
-    }
-  } else if (n > 0) {
-    if ((rc = copy_small(h->d_rest + h->nrest, dx, n, st))) return rc;
-  }
+  if (B > 0) rc = copy_small(h->d_rest, dx + (B * Ne - h->nrest), left, st);      // lies inside x (B >= 1): rest is only written
+  else rc = copy_small(h->d_rest + h->nrest, dx, n, st);
+  if (rc) return rc;
   h->nrest = left;
   h->pending_blocks = (int) B;
   if (dxv != x) TSD_HIP(hipStreamSynchronize(st));   // the staging buffer is reused by the next call
@@ -1147,118 +1250,10 @@ int tsdgpu_ola_step(tsdgpu_ola *h, const void *x, int64_t n, void *y, int64_t *n
         x, n, sizeof(cpx), y, sizeof(cpx), n_out, Ne, (hipStream_t) stream, [Ne](int64_t c) { return c + Ne; },
         [h](const void *cx, void *cy, int64_t cnt, int64_t, int64_t *got, hipStream_t q) { return tsdgpu_ola_step(h, cx, cnt, cy, got, q); });
   }
-  if (h->d_fast && !h->windowed && h->nrest == 0 && n >= h->Ne && h->pending_blocks < 0 && x != nullptr && y != nullptr) {
-    // fast path: B whole blocks through ONE kernel, 16 B of HBM traffic per sample (see ols.hip)
-    hipStream_t st = (hipStream_t) stream;
-    const int Ne = h->Ne;
-    const int64_t B = n / Ne, nout = B * Ne, left = n - nout;
-    if (n_out) *n_out = 0;
-    const void *dxv = nullptr;
-    void *dyv = nullptr;
-    bool staged = false;
-    int rc = stage_in(x, (size_t) n * sizeof(cpx), h->in_stage, st, &dxv);
-    if (rc) return rc;
-    if ((rc = stage_out(y, (size_t) nout * sizeof(cpx), h->out_stage, &dyv, &staged))) return rc;
-    if (dxv == dyv) {
-      // in place on the device: a run re-reads the block before it, which the run before may already have overwritten
-      if ((rc = h->in_stage.reserve((size_t) n * sizeof(cpx)))) return rc;
-      TSD_HIP(hipMemcpyAsync(h->in_stage.p, dxv, (size_t) n * sizeof(cpx), hipMemcpyDeviceToDevice, st));
-      dxv = h->in_stage.p;
-    }
-    const cpx *dx = (const cpx *) dxv;
-    if ((rc = copy_small(h->d_rest, dx + nout, left, st))) return rc;
-    if ((rc = ola1024_launch(dx, (cpx *) dyv, h->d_fast, h->d_svg, h->d_svg_tmp, B, st))) return rc;
-    std::swap(h->d_svg, h->d_svg_tmp);            // (the last wave wrote the new tail beside the one the first wave read)
-    if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
-    h->nrest = (int) left;
-    h->cnt_ech += nout;
-    if (n_out) *n_out = nout;
-    return TSDGPU_OK;
-  }
-  if (h->d_run && !h->windowed && h->pending_blocks < 0 && n >= 0 && (n == 0 || x != nullptr) && ((int64_t) h->nrest + n) / h->Ne >= 1 && y != nullptr) {
-    // any other geometry without window: B whole blocks of [rest ++ x] through ONE kernel (ola_run_kernel)
-    hipStream_t st = (hipStream_t) stream;
-    const int Ne = h->Ne;
-    const int64_t tot = (int64_t) h->nrest + n, B = tot / Ne, nout = B * Ne, left = tot - nout;
-    if (n_out) *n_out = 0;
-    TSD_CHECK(B <= (1 << 24), "ola_step: %lld blocks in one call", (long long) B);
-    const void *dxv = nullptr;
-    void *dyv = nullptr;
-    bool staged = false;
-    int rc = stage_in(x, (size_t) n * sizeof(cpx), h->in_stage, st, &dxv);
-    if (rc) return rc;
-    if ((rc = stage_out(y, (size_t) nout * sizeof(cpx), h->out_stage, &dyv, &staged))) return rc;
-    if (host_ranges_overlap(dxv, (size_t) n * sizeof(cpx), dyv, (size_t) nout * sizeof(cpx))) {
-      // in place on the device: a run re-reads the block before it, which the run before may already have overwritten
-      if ((rc = h->in_stage.reserve((size_t) n * sizeof(cpx)))) return rc;
-      TSD_HIP(hipMemcpyAsync(h->in_stage.p, dxv, (size_t) n * sizeof(cpx), hipMemcpyDeviceToDevice, st));
-      dxv = h->in_stage.p;
-    }
-    const cpx *dx = (const cpx *) dxv;
-    // block 0 made contiguous: the waiting samples, then the head of x (rest has room for a whole block)
-    if (h->nrest > 0 && (rc = copy_small(h->d_rest + h->nrest, dx, Ne - h->nrest, st))) return rc;
-    if ((rc = ola_run_launch(h->nrest > 0 ? h->d_rest : dx, h->nrest, dx, (cpx *) dyv, h->d_run, h->d_svg, h->d_svg_tmp, Ne, h->N, B, st))) return rc;
-    std::swap(h->d_svg, h->d_svg_tmp);
-    if (left > 0) {
-      // the samples after the last whole block lie inside x (B >= 1): rest is only written
-      hipLaunchKernelGGL(ola_gather_kernel, dim3(nblk(left)), dim3(256), 0, st, h->d_rest, 0, dx, nout - h->nrest, h->d_rest, (int) left);
-      TSD_HIP(hipGetLastError());
-    }
-    if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
-    h->nrest = (int) left;
-    h->cnt_ech += nout;
-    if (n_out) *n_out = nout;
-    return TSDGPU_OK;
-  }
-  if (h->d_run && h->windowed && h->pending_blocks < 0 && n >= 0 && (n == 0 || x != nullptr) && ((int64_t) h->nrest + n) / h->Ne >= 1 && y != nullptr) {
-    // the windowed mode: B whole blocks of [rest ++ x] through ONE kernel (olaw_run_kernel)
-    hipStream_t st = (hipStream_t) stream;
-    const int Ne = h->Ne;
-    const int64_t tot = (int64_t) h->nrest + n, B = tot / Ne, left = tot - B * Ne;
-    const int skip = h->cnt_ech < 0 ? 1 : 0;                       // (:899-901: the very first block gives no output)
-    const int64_t nout = (B - skip) * Ne;
-    if (n_out) *n_out = 0;
-    TSD_CHECK(B <= (1 << 24), "ola_step: %lld blocks in one call", (long long) B);
-    const void *dxv = nullptr;
-    void *dyv = nullptr;
-    bool staged = false;
-    int rc = stage_in(x, (size_t) n * sizeof(cpx), h->in_stage, st, &dxv);
-    if (rc) return rc;
-    if ((rc = stage_out(y, (size_t) nout * sizeof(cpx), h->out_stage, &dyv, &staged))) return rc;
-    if (nout > 0 && host_ranges_overlap(dxv, (size_t) n * sizeof(cpx), dyv, (size_t) nout * sizeof(cpx))) {
-      // in place on the device: a run re-reads the blocks before it, which the run before may already have overwritten
-      if ((rc = h->in_stage.reserve((size_t) n * sizeof(cpx)))) return rc;
-      TSD_HIP(hipMemcpyAsync(h->in_stage.p, dxv, (size_t) n * sizeof(cpx), hipMemcpyDeviceToDevice, st));
-      dxv = h->in_stage.p;
-    }
-    const cpx *dx = (const cpx *) dxv;
-    // block 0 made contiguous: the waiting samples, then the head of x (rest has room for a whole block)
-    if (h->nrest > 0 && (rc = copy_small(h->d_rest + h->nrest, dx, Ne - h->nrest, st))) return rc;
-    if (h->d_fast && h->N == 512 && Ne == 512)
-      rc = olaw512_launch(h->nrest > 0 ? h->d_rest : dx, h->nrest, dx, (cpx *) dyv, h->d_fast, h->d_fen, h->d_svg, h->d_last, h->d_prev_half,
-                          h->d_svg_tmp, h->d_last_tmp, B, skip, st);
-    else
-      rc = olaw_run_launch(h->nrest > 0 ? h->d_rest : dx, h->nrest, dx, (cpx *) dyv, h->d_run, h->d_fen, h->d_svg, h->d_last, h->d_prev_half,
-                           h->d_svg_tmp, h->d_last_tmp, Ne, h->N, B, skip, st);
-    if (rc) return rc;
-    std::swap(h->d_svg, h->d_svg_tmp);
-    std::swap(h->d_last, h->d_last_tmp);
-    // the second half of the last block waits for the next call's first frame (:926); then the samples after the last whole block
-    hipLaunchKernelGGL(ola_gather_kernel, dim3(nblk(Ne / 2)), dim3(256), 0, st, h->d_rest, h->nrest, dx, (B - 1) * Ne + Ne / 2, h->d_prev_half, Ne / 2);
-    TSD_HIP(hipGetLastError());
-    if (left > 0) {
-      hipLaunchKernelGGL(ola_gather_kernel, dim3(nblk(left)), dim3(256), 0, st, h->d_rest, 0, dx, B * Ne - h->nrest, h->d_rest, (int) left);
-      TSD_HIP(hipGetLastError());
-    }
-    if ((rc = finish_out(y, (size_t) nout * sizeof(cpx), dyv, staged, st))) return rc;
-    if (dxv != x && !staged && !is_device_ptr(x)) TSD_HIP(hipStreamSynchronize(st));    // (an input staged from the HOST must outlive its kernels; the in-place copy of a device x is ordered on st like every later use of in_stage)
-    h->nrest = (int) left;
-    h->cnt_ech += B * Ne;
-    if (n_out) *n_out = nout;
-    return TSDGPU_OK;
-  }
+  // a response whose geometry has a fused kernel, and at least one whole block: ONE kernel
+  if (h->d_run && h->pending_blocks < 0 && n >= 0 && (n == 0 || x != nullptr) && y != nullptr && ((int64_t) h->nrest + n) / h->Ne >= 1)
+    return ola_fused_step(h, x, n, y, n_out, (hipStream_t) stream);
+  // the multi-kernel engine: framed transform with the response, inverse transform, overlap-add
   void *sp = nullptr;
   int nf = 0;
   h->fuse_response = true;
@@ -1280,174 +1275,111 @@ int tsdgpu_welch(const void *x, int64_t n, int N, const float *window, float *S,
   if (n > N) nseg = (n - N - 1) / pas + 1;                         // i = 0, pas, ... while i + N < n  (:13)
   if (n_segments) *n_segments = nseg;
   TSD_CHECK(nseg <= 0x7fffffff, "welch: %lld segments in one call", (long long) nseg);
-  // scratch and plan borrowed for the call (the one-shot API used to spend most of its time in hipMalloc / hipFree and in
-  // building the plan)
-  struct Ctx {
-    int dev = 0, N = 0, lots = 0;
-    tsdgpu_fft *plan = nullptr;
-    DevBuf xin, seg, part, wbuf, sout, tw;
-    int tw_N = 0;                     // the size the transform tables in tw were made for (0: none)
-    void libere() { if (plan) tsdgpu_fft_destroy(plan); xin.release(); seg.release(); part.release(); wbuf.release(); sout.release(); tw.release(); }
-    size_t octets() const { return xin.cap + seg.cap + part.cap + wbuf.cap + sout.cap; }
-  };
-  static CtxReserve<Ctx> *reserve = new CtxReserve<Ctx>(4);
-  Ctx *c = reserve->prend([N](const Ctx &k) { return k.N == N || k.tw_N == N; });
-  DevBuf &xin = c->xin, &seg = c->seg, &part = c->part, &wbuf = c->wbuf, &sout = c->sout;
-  const void *dxv = nullptr, *dwv = nullptr;
-  void *dS = nullptr;
-  bool staged = false;
-  int rc = stage_in(x, (size_t) n * sizeof(cpx), xin, st, &dxv);
-  if (!rc) rc = stage_in(window, (size_t) N * sizeof(float), wbuf, st, &dwv);
-  if (!rc) rc = stage_out(S, (size_t) N * sizeof(float), sout, &dS, &staged);
-  tsdgpu_fft *plan = nullptr;
+  static CtxReserve<WelchCtx> *reserve = new CtxReserve<WelchCtx>(4);
+  WelchCtx *c = reserve->prend([N](const WelchCtx &k) { return k.N == N || k.tw_N == N; });
+  // the scratch buffers go back whichever way the call ends, once the work that uses them is done
+  struct Rend {
+    WelchCtx *c;
+    hipStream_t st;
+    ~Rend()
+    {
+      (void) hipStreamSynchronize(st);
+      reserve->rend(c);
+    }
+  } rend{c, st};
   static const bool multi = dev_switch("OLA_UNFUSED") != nullptr;
-  if (!rc && nseg > 0 && N == 1024 && !multi) {
-    // N = 1024: ONE kernel on the in-wave transform keeps the running sums in registers (ols.hip, welch1024_kernel)
-    if (c->tw_N != 1024) {
-      std::vector<cpx> t2(2048);
-      welch1024_tables(t2.data());
-      c->tw_N = 0;
-      rc = c->tw.reserve(t2.size() * sizeof(cpx));
-      if (!rc && hipMemcpy(c->tw.p, t2.data(), t2.size() * sizeof(cpx), hipMemcpyHostToDevice) != hipSuccess)
-        rc = set_err(TSDGPU_ERR_HIP, "welch: table upload failed");
-      if (!rc) c->tw_N = 1024;
-    }
-    const int per = (int) std::min<int64_t>(64, std::max<int64_t>(1, cdiv(nseg, 2048)));       // (rounded UP: 2048 waves are resident at once; one more is a second, nearly empty round)
-    const int64_t rows = cdiv(nseg, per);
-    // the rows of the waves are summed in two deterministic stages (a single stage would walk thousands of rows from
-    // four workgroups)
-    // (groups of 8 rows over many workgroups, then 4 row lanes per bin: the 64-group form -- 35 rows per thread from 256 workgroups, then
-    // 64 rows per thread from four -- took 27 + 16 us of the call's 118)
-    const int rpg = (int) std::min<int64_t>(64, std::max<int64_t>(8, cdiv(rows, 96))), ngr = (int) cdiv(rows, rpg);
-    if (!rc) rc = part.reserve((size_t) (rows + ngr) * N * sizeof(float));
-    float *p1 = part.as<float>(), *p2 = p1 + (size_t) rows * N;
-    if (!rc) rc = welch1024_launch((const cpx *) dxv, (const float *) dwv, c->tw.as<cpx>(), p1, nseg, per, st);
-    if (!rc) {
-      hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) ngr), dim3(256), 0, st, p1, p2, N, (int) rows, rpg);
-      hipLaunchKernelGGL(welch_sum_shift_kernel, dim3((unsigned) cdiv(N, 64)), dim3(256), 0, st, p2, (float *) dS, N, ngr, 0);
-      if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
-    }
-    if (!rc) rc = finish_out(S, (size_t) N * sizeof(float), dS, staged, st);
-    (void) hipStreamSynchronize(st);
-    reserve->rend(c);
-    return rc;
-  }
-  if (!rc && nseg > 0 && !multi && N >= 16 && (N & (N - 1)) == 0 && ola_run_fits(N, N / 2)) {
-    // the other powers of two up to 16384: ONE kernel on the LDS transform keeps the running sums in registers (welch_run_kernel)
-    if (c->tw_N != N) {
-      std::vector<cpx> tw((size_t) N / 16);
-      const double PI = 3.14159265358979323846;
-      for (int i = 0; i < N / 16; i++) {
-        const double a = -2.0 * PI * (double) i / (double) N;
-        tw[i] = make_float2((float) std::cos(a), (float) std::sin(a));
-      }
-      c->tw_N = 0;
-      rc = c->tw.reserve(tw.size() * sizeof(cpx));
-      if (!rc && hipMemcpy(c->tw.p, tw.data(), tw.size() * sizeof(cpx), hipMemcpyHostToDevice) != hipSuccess)
-        rc = set_err(TSDGPU_ERR_HIP, "welch: table upload failed");
-      if (!rc) c->tw_N = N;
-    }
-    const OlaRunGeom g = ola_run_geom(N, N / 2);
-    static const int cus = []() {
-      int dev = 0, n = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-      return n > 0 ? n : 256;
-    }();
-    // one pass of the chip: a run per (resident workgroup x transform)
-    const int64_t places = (int64_t) cus * (g.threads == 256 ? 3 : 1) * g.T;
-    const int per = (int) std::min<int64_t>(64, std::max<int64_t>(1, cdiv(nseg, places)));
-    const int64_t rows = cdiv(nseg, per);
-    const int rpg = (int) std::min<int64_t>(64, std::max<int64_t>(8, cdiv(rows, 96))), ngr = (int) cdiv(rows, rpg);
-    if (!rc) rc = part.reserve((size_t) (rows + ngr) * N * sizeof(float));
-    float *p1 = part.as<float>(), *p2 = p1 + (size_t) rows * N;
-    if (!rc) rc = welch_run_launch((const cpx *) dxv, (const float *) dwv, c->tw.as<cpx>(), p1, N, nseg, per, st);
-    if (!rc) {
-      hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) ngr), dim3(256), 0, st, p1, p2, N, (int) rows, rpg);
-      hipLaunchKernelGGL(welch_sum_shift_kernel, dim3((unsigned) cdiv(N, 64)), dim3(256), 0, st, p2, (float *) dS, N, ngr, 0);
-      if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
-    }
-    if (!rc) rc = finish_out(S, (size_t) N * sizeof(float), dS, staged, st);
-    (void) hipStreamSynchronize(st);
-    reserve->rend(c);
-    return rc;
-  }
-  if (!rc && nseg > 0 && !(c->plan && c->N == N)) {        // (the batch count given at creation is only a hint)
-    if (c->plan) tsdgpu_fft_destroy(c->plan);
-    c->plan = nullptr;
-    c->N = c->lots = 0;
-    rc = tsdgpu_fft_create(&c->plan, N, (int) nseg);
-    if (!rc) { c->N = N; c->lots = (int) nseg; }
-  }
-  plan = c->plan;
-  if (!rc && nseg == 0) {
+  DevBuf &seg = c->seg, &part = c->part;
+  const void *dxv = nullptr, *dwv = nullptr;
+  void *dSv = nullptr;
+  bool staged = false;
+  int rc = stage_in(x, (size_t) n * sizeof(cpx), c->xin, st, &dxv);
+  if (!rc) rc = stage_in(window, (size_t) N * sizeof(float), c->wbuf, st, &dwv);
+  if (!rc) rc = stage_out(S, (size_t) N * sizeof(float), c->sout, &dSv, &staged);
+  if (rc) return rc;
+  const cpx *dx = (const cpx *) dxv;
+  const float *dw = (const float *) dwv;
+  float *dS = (float *) dSv;
+  // A fused producer leaves `rows` rows of partial sums in part (its caller has reserved them, welch_rows_layout), in fftshift
+  // order or, shift = 1, in transform order; the one reduction after the branches sums them into S.
+  int64_t rows = 0;
+  int shift = 0;
+  WelchRows L;
+  if (nseg == 0) {
     if (hipMemsetAsync(dS, 0, (size_t) N * sizeof(float), st) != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: memset failed");
-  } else if (!rc) {
+  } else if (!multi && N == 1024) {
+    // N = 1024: ONE kernel on the in-wave transform keeps the running sums in registers (ols.hip, welch1024_kernel)
+    const int per = (int) std::min<int64_t>(64, std::max<int64_t>(1, cdiv(nseg, 2048)));       // (rounded UP: 2048 waves are resident at once; one more is a second, nearly empty round)
+    rows = cdiv(nseg, per);
+    rc = welch_tables(c, N);
+    if (!rc) rc = welch_rows_layout(part, rows, N, &L);
+    if (!rc) rc = welch1024_launch(dx, dw, c->tw.as<cpx>(), L.p1, nseg, per, st);
+  } else if (!multi && N >= 16 && (N & (N - 1)) == 0 && ola_run_fits(N, N / 2)) {
+    // the other powers of two up to 16384: ONE kernel on the LDS transform keeps the running sums in registers (welch_run_kernel)
+    const OlaRunGeom g = ola_run_geom(N, N / 2);
+    // one pass of the chip: a run per (resident workgroup x transform)
+    const int64_t places = (int64_t) cu_count() * (g.threads == 256 ? 3 : 1) * g.T;
+    const int per = (int) std::min<int64_t>(64, std::max<int64_t>(1, cdiv(nseg, places)));
+    rows = cdiv(nseg, per);
+    rc = welch_tables(c, N);
+    if (!rc) rc = welch_rows_layout(part, rows, N, &L);
+    if (!rc) rc = welch_run_launch(dx, dw, c->tw.as<cpx>(), L.p1, N, nseg, per, st);
+  } else {
+    if (!(c->plan && c->N == N)) {        // (the batch count given at creation is only a hint)
+      if (c->plan) tsdgpu_fft_destroy(c->plan);
+      c->plan = nullptr;
+      c->N = c->lots = 0;
+      if ((rc = tsdgpu_fft_create(&c->plan, N, (int) nseg))) return rc;
+      c->N = N;
+      c->lots = (int) nseg;
+    }
+    tsdgpu_fft *plan = c->plan;
     // sizes whose plan is the wave-level Bluestein (N = 1000 = 8 x 125, odd N <= 511 ...): that kernel frames, windows, transforms and
-    // sums |X|^2 per workgroup; what is left is the reduction of its partial rows
-    int64_t rows = 0;
-    if (!multi) rc = fft_blu_framed_launch(plan, (const cpx *) dxv, pas, (const float *) dwv, nseg, nullptr, 0, &rows, st);
+    // sums |X|^2 per workgroup (one row per workgroup of its persistent grid: a few hundred); the first call only asks for the row count
+    if (!multi) rc = fft_blu_framed_launch(plan, dx, pas, dw, nseg, nullptr, 0, &rows, st);
     if (!rc && rows > 0) {
-      // (one row per workgroup of the persistent grid: a few hundred; groups of 8 rows, then 4 row lanes per bin)
-      const int rpg = (int) std::min<int64_t>(64, std::max<int64_t>(8, cdiv(rows, 96))), ngr = (int) cdiv(rows, rpg);
-      rc = part.reserve((size_t) (rows + ngr) * N * sizeof(float));
-      float *p1 = part.as<float>(), *p2 = p1 + (size_t) rows * N;
-      if (!rc) rc = fft_blu_framed_launch(plan, (const cpx *) dxv, pas, (const float *) dwv, nseg, p1, rows, &rows, st);
+      shift = 1;
+      rc = welch_rows_layout(part, rows, N, &L);
+      if (!rc) rc = fft_blu_framed_launch(plan, dx, pas, dw, nseg, L.p1, rows, &rows, st);
+    } else if (!rc) {
+      const int64_t total = nseg * N;
+      // enough groups to fill the chip whatever N: N/256 x groups workgroups, <= 512 partial sums per bin
+      const int groups = (int) std::max<int64_t>(1, std::min<int64_t>(512, std::min<int64_t>(cdiv(nseg, 16), cdiv(262144, N))));
+      const int64_t per_group = cdiv(nseg, groups);
+      rc = seg.reserve((size_t) total * sizeof(cpx));
+      if (!rc) rc = part.reserve((size_t) (groups + 64) * N * sizeof(float));       // + the rows of the second summation stage
+      bool fused = false;
       if (!rc) {
-        hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) ngr), dim3(256), 0, st, p1, p2, N, (int) rows, rpg);
-        hipLaunchKernelGGL(welch_sum_shift_kernel, dim3((unsigned) cdiv(N, 64)), dim3(256), 0, st, p2, (float *) dS, N, ngr, 1);
+        // fused: segments gathered and windowed by the transform itself, which stores |X|^2 only
+        const FrameSrc F{nullptr, dx, nullptr, dw, 0, pas, N, 0, 2};
+        fused = framed_fft_launch(plan, F, nseg, nullptr, nullptr, seg.as<float>(), st);
+      }
+      if (!rc && !fused) {
+        hipLaunchKernelGGL(welch_frame_kernel, dim3(nblk(total)), dim3(256), 0, st, dx, dw, seg.as<cpx>(), N, pas, total);
+        if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
+        if (!rc) rc = tsdgpu_fft_step(plan, seg.p, seg.p, (int) nseg, 1, st);
+      }
+      if (!rc) {
+        if (fused)
+          hipLaunchKernelGGL(welch_power_sum_kernel, dim3(nblk(N), (unsigned) groups), dim3(256), 0, st, seg.as<float>(),
+                             part.as<float>(), N, nseg, per_group);
+        else
+          hipLaunchKernelGGL(welch_power_kernel, dim3(nblk(N), (unsigned) groups), dim3(256), 0, st, seg.as<cpx>(), part.as<float>(), N,
+                             nseg, per_group);
+        if (groups > 64) {
+          // (two deterministic stages: one stage would walk hundreds of rows from N / 256 workgroups)
+          const int rpg = (int) cdiv(groups, 64), ngr = (int) cdiv(groups, rpg);
+          float *p2 = part.as<float>() + (size_t) groups * N;
+          hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) ngr), dim3(256), 0, st, part.as<float>(), p2, N, groups, rpg);
+          hipLaunchKernelGGL(welch_sum_kernel, dim3(nblk(N)), dim3(256), 0, st, p2, dS, N, ngr);
+        } else {
+          hipLaunchKernelGGL(welch_sum_kernel, dim3(nblk(N)), dim3(256), 0, st, part.as<float>(), dS, N, groups);
+        }
         if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
       }
-      if (!rc) rc = finish_out(S, (size_t) N * sizeof(float), dS, staged, st);
-      (void) hipStreamSynchronize(st);
-      reserve->rend(c);
-      return rc;
-    }
-    if (rc) {
-      (void) hipStreamSynchronize(st);
-      reserve->rend(c);
-      return rc;
-    }
-    const int64_t total = nseg * N;
-    // enough groups to fill the chip whatever N: N/256 x groups workgroups, <= 512 partial sums per bin
-    const int groups = (int) std::max<int64_t>(1, std::min<int64_t>(512, std::min<int64_t>(cdiv(nseg, 16), cdiv(262144, N))));
-    const int64_t per_group = cdiv(nseg, groups);
-    rc = seg.reserve((size_t) total * sizeof(cpx));
-    if (!rc) rc = part.reserve((size_t) (groups + 64) * N * sizeof(float));       // + the rows of the second summation stage
-    bool fused = false;
-    if (!rc) {
-      // fused: segments gathered and windowed by the transform itself, which stores |X|^2 only
-      const FrameSrc S{nullptr, (const cpx *) dxv, nullptr, (const float *) dwv, 0, pas, N, 0, 2};
-      fused = framed_fft_launch(plan, S, nseg, nullptr, nullptr, seg.as<float>(), st);
-    }
-    if (!rc && !fused) {
-      hipLaunchKernelGGL(welch_frame_kernel, dim3(nblk(total)), dim3(256), 0, st, (const cpx *) dxv, (const float *) dwv,
-                         seg.as<cpx>(), N, pas, total);
-      if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
-      if (!rc) rc = tsdgpu_fft_step(plan, seg.p, seg.p, (int) nseg, 1, st);
-    }
-    if (!rc) {
-      if (fused)
-        hipLaunchKernelGGL(welch_power_sum_kernel, dim3(nblk(N), (unsigned) groups), dim3(256), 0, st, seg.as<float>(),
-                           part.as<float>(), N, nseg, per_group);
-      else
-        hipLaunchKernelGGL(welch_power_kernel, dim3(nblk(N), (unsigned) groups), dim3(256), 0, st, seg.as<cpx>(), part.as<float>(), N,
-                           nseg, per_group);
-      if (groups > 64) {
-        // (two deterministic stages: one stage would walk hundreds of rows from N / 256 workgroups)
-        const int rpg = (int) cdiv(groups, 64), ngr = (int) cdiv(groups, rpg);
-        float *p2 = part.as<float>() + (size_t) groups * N;
-        hipLaunchKernelGGL(welch_sum_groups_kernel, dim3(nblk(N), (unsigned) ngr), dim3(256), 0, st, part.as<float>(), p2, N, groups, rpg);
-        hipLaunchKernelGGL(welch_sum_kernel, dim3(nblk(N)), dim3(256), 0, st, p2, (float *) dS, N, ngr);
-      } else {
-        hipLaunchKernelGGL(welch_sum_kernel, dim3(nblk(N)), dim3(256), 0, st, part.as<float>(), (float *) dS, N, groups);
-      }
-      if (hipGetLastError() != hipSuccess) rc = set_err(TSDGPU_ERR_HIP, "welch: launch failed");
     }
   }
-  if (!rc) rc = finish_out(S, (size_t) N * sizeof(float), dS, staged, st);
-  // the scratch buffers die with the call: wait for the work that uses them
-  (void) hipStreamSynchronize(st);
-  reserve->rend(c);
+  if (!rc && rows > 0) rc = welch_reduce_rows(part, rows, N, shift, dS, st);
+  if (!rc) rc = finish_out(S, (size_t) N * sizeof(float), dSv, staged, st);
   return rc;
 }
 
@@ -1503,12 +1435,10 @@ int tsdgpu_spectrum_create(tsdgpu_spectrum **out, int BS, int nsubs, int nmeans,
   } else {
     for (int j = 0; j < Ns; j++) cnt[j] = 1.f;
   }
-  float *tw = cnt + Ns + 2 * (size_t) ncls * Nf;
-  const double PI = 3.14159265358979323846;
-  for (size_t i = 0; i < ntw; i++) {
-    const double a = -2.0 * PI * (double) i / (double) Nf;
-    tw[2 * i] = (float) std::cos(a);
-    tw[2 * i + 1] = (float) std::sin(a);
+  if (h->run_kernel) {
+    std::vector<cpx> tw(ntw);
+    fill_w16(tw.data(), Nf);
+    std::memcpy(cnt + Ns + 2 * (size_t) ncls * Nf, tw.data(), ntw * sizeof(cpx));
   }
   int rc = TSDGPU_OK;
   if (hipMalloc((void **) &h->d_tab, img.size() * sizeof(float)) != hipSuccess)
@@ -1580,15 +1510,10 @@ static int spectrum_step_blocks(tsdgpu_spectrum *h, const void *x, int64_t nbloc
   // runs: a class = the segments that are summed into one spectrum (sweep: one per sub-block index)
   const int ncls = h->sweep ? nsubs : 1;
   const int64_t per_class = h->sweep ? nmeans : (int64_t) nmeans * nsubs;         // segments of a full class
-  static const int cus = []() {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
   int64_t places = 4096;
   if (h->run_kernel) {
     const OlaRunGeom g = ola_run_geom(Nf, Nf / 2);
-    places = (int64_t) cus * (g.threads == 256 ? 3 : 1) * g.T;
+    places = (int64_t) cu_count() * (g.threads == 256 ? 3 : 1) * g.T;
   }
   const int per = (int) std::min<int64_t>(std::min<int64_t>(64, per_class), std::max<int64_t>(1, cdiv(S, places)));
   const int rpg = (int) cdiv(per_class, per);

@@ -291,3 +291,28 @@ def test_fused_windowed_long_runs(Ne, nz):
     g4.set_response(H)
     xs = x[:40 * Ne + 11].cpu().numpy()
     assert relerr(g4.step(xs), ref.step(xs)) <= TOL
+
+
+@pytest.mark.parametrize("Ne,K,B,off", [(512, 127, 8, 1), (2048, 127, 8, 1), (512, 127, 40000, 16384)])
+def test_output_partly_over_the_input(Ne, K, B, off):
+    """y starts `off` blocks into x: neither disjoint nor the same buffer.  Every fused kernel re-reads blocks that an earlier
+    run's output may already lie on, so the step takes its private copy of x for ANY overlap, the in-wave default geometry
+    (512 / 1024) like the run kernel (2048 / 4096): the same bits as the same handle state run out of place.  (The 8-block calls
+    pin the rule; without the copy they still come out right, every wave of so short a call having read its blocks before the
+    first one stores.  The 40000 blocks are 2500 runs of 16 for 2048 resident waves: the second round would read, 16384 blocks
+    on, what the first wrote.)"""
+    import torch
+    rng = np.random.default_rng(13)
+    H, _ = response(t.Ola(Ne, K, None).N, rng, K)
+    warm = torch.from_numpy(randc(rng, Ne)).cuda()
+    x = torch.view_as_complex(torch.randn(B * Ne, 2, device="cuda", generator=torch.Generator(device="cuda").manual_seed(B)))
+    ys = []
+    for over in (False, True):
+        g = t.Ola(Ne, K, None)
+        g.set_response(H)
+        g.step(warm)                                         # (a carried tail that is not zero)
+        buf = torch.zeros((B + off) * Ne, dtype=torch.complex64, device="cuda")
+        buf[:B * Ne] = x
+        ys.append(g.step(buf[:B * Ne], buf[off * Ne:] if over else torch.empty_like(x)).clone())
+    assert ys[0].shape[0] == B * Ne and float(ys[0].abs().max()) > 0
+    assert torch.equal(ys[1], ys[0])
