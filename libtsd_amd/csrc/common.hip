@@ -461,6 +461,17 @@ int pipelined_host_step_var(const void *x, int64_t n, size_t esz_in, void *y, si
   return TSDGPU_OK;
 }
 
+int DevImage::upload(const char *entry)
+{
+  if (hipMalloc((void **) &d, host.size()) != hipSuccess) {
+    d = nullptr;
+    return set_err(TSDGPU_ERR_HIP, "%s: hipMalloc failed: %s", entry, hipGetErrorString(hipGetLastError()));
+  }
+  if (hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return set_err(TSDGPU_ERR_HIP, "%s: upload failed: %s", entry, hipGetErrorString(hipGetLastError()));
+  return TSDGPU_OK;
+}
+
 const char *dev_switch(const char *name)
 {
   char key[96];

@@ -53,6 +53,23 @@ struct DevBuf {
   template <typename T> T *as() const { return static_cast<T *>(p); }
 };
 
+// A handle's constant device memory as ONE allocation and ONE upload: segments that start at 16-byte boundaries are reserved (zeroed)
+// in a host image and filled there; upload() does the hipMalloc and the hipMemcpy (a one-shot rééchan() pays for every creation: an
+// allocation, a copy and a memset per table and history cost it a third of its time).  dev(0) is the caller's to hipFree, also after a failed upload.
+struct DevImage {
+  std::vector<char> host;
+  char *d = nullptr;
+  size_t reserve(size_t bytes)                                  // -> the segment's offset
+  {
+    const size_t off = (host.size() + 15) / 16 * 16;
+    host.resize(off + bytes, 0);
+    return off;
+  }
+  template <typename T> T *at(size_t off) { return reinterpret_cast<T *>(host.data() + off); }
+  int upload(const char *entry);                                // errors read "<entry>: hipMalloc failed: ..." / "<entry>: upload failed: ..."
+  template <typename T = void> T *dev(size_t off) const { return d ? reinterpret_cast<T *>(d + off) : nullptr; }
+};
+
 // Presents a (host or device) input as a device pointer; host data is copied to `buf`.
 int stage_in(const void *src, size_t bytes, DevBuf &buf, hipStream_t st, const void **dev);
 // Gives a device pointer to write the output to: `dst` itself when it is device memory,
@@ -176,6 +193,8 @@ template <int V, int... Vs, typename FN> auto int_switch(int v, FN fn)
     return int_switch<Vs...>(v, fn);
   }
 }
+// the same for a handle's data_type: fn(float()) for TSDGPU_F32, fn(float2()) for TSDGPU_C64 -- `using T = decltype(tag);` in fn
+template <typename FN> auto type_switch(int data_type, FN fn) { return data_type != TSDGPU_C64 ? fn(float()) : fn(float2()); }
 // the radix of the first pass of a 2^log2n-point radix-16 Stockham transform (stockham16.hpp), 2, 4, 8 or 16, and fn(int_c<R0>())
 // for that radix
 inline int first_radix(int log2n) { return 1 << ((log2n & 3) == 0 ? 4 : (log2n & 3)); }

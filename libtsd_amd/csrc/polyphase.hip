@@ -693,89 +693,90 @@ int fused_setup(tsdgpu_polyfir *p, const std::vector<float> &g, int NPH, int W, 
   p->NPH = NPH;
   p->W = W;
   p->HW = std::max(W - 1, 1);
-  // ONE allocation -- the taps, then the two (zero) histories, 16-byte aligned -- and ONE upload of its host image (three
-  // allocations, a copy, two memsets and a synchronisation before: a third of a one-shot rééchan(x, 4))
-  const size_t hb = ((size_t) p->HW * dtype_size(p->data_type) + 15) / 16 * 16, gb = (g.size() * sizeof(float) + 15) / 16 * 16;
   // decimators of rate 2 / 4 / 8 up to 64 taps: the reversed, padded taps of decim_direct_kernel behind the histories
   // ... and upsamplers of rate 2 / 4 with branches of up to 32 taps (ups_direct_kernel): one such row per branch
   const bool direct = poly_direct_regime(NPH, W, stride) && dev_switch("POLY_NO_DIRECT") == nullptr;
   p->KPd = direct ? poly_direct_kp(W, p->data_type) : 0;
-  const size_t rb = (size_t) p->KPd * NPH * sizeof(float);
-  std::vector<char> image(gb + 2 * hb + rb, 0);
-  std::memcpy(image.data(), g.data(), g.size() * sizeof(float));
-  if (direct) poly_direct_rows(g, NPH, W, p->KPd, reinterpret_cast<float *>(image.data() + gb + 2 * hb));   // hrev[j] = g[KP - 1 - j]
-  if (hipMalloc((void **) &p->d_g, image.size()) != hipSuccess)
-    return set_err(TSDGPU_ERR_HIP, "polyfir_create: hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
-  p->d_hist[0] = (char *) p->d_g + gb;
-  p->d_hist[1] = (char *) p->d_g + gb + hb;
-  p->d_hrev = direct ? reinterpret_cast<float *>((char *) p->d_g + gb + 2 * hb) : nullptr;
-  if (hipMemcpy(p->d_g, image.data(), image.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return set_err(TSDGPU_ERR_HIP, "polyfir_create: upload failed: %s", hipGetErrorString(hipGetLastError()));
-  (void) hipFuncSetAttribute((const void *) polyfir_fused_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) polyfir_fused_kernel<float2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  // the taps, then the two (zero) histories, then the rows
+  DevImage img;
+  const size_t hb = (size_t) p->HW * dtype_size(p->data_type);
+  const size_t o_g = img.reserve(g.size() * sizeof(float)), o_h0 = img.reserve(hb), o_h1 = img.reserve(hb),
+               o_rows = img.reserve((size_t) p->KPd * NPH * sizeof(float));
+  std::memcpy(img.at<float>(o_g), g.data(), g.size() * sizeof(float));
+  if (direct) poly_direct_rows(g, NPH, W, p->KPd, img.at<float>(o_rows));   // hrev[j] = g[KP - 1 - j]
+  const int rc = img.upload("polyfir_create");
+  p->d_g = img.dev<float>(o_g);
+  if (rc) return rc;
+  p->d_hist[0] = img.dev(o_h0);
+  p->d_hist[1] = img.dev(o_h1);
+  p->d_hrev = direct ? img.dev<float>(o_rows) : nullptr;
+  type_switch(p->data_type, [&](auto tag) {      // (on the device that holds the handle's memory)
+    using T = decltype(tag);
+    const void *ups = int_switch<2, 4>(NPH, [](auto nph) { return (const void *) ups_direct_kernel<T, 64 / (int) sizeof(T), decltype(nph)::value>; });
+    for (const void *k : {(const void *) polyfir_fused_kernel<T>, p->d_hrev && NPH > 1 ? ups : nullptr})
+      if (k) (void) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  });
   (void) hipGetLastError();
   p->fused = true;
   return TSDGPU_OK;
 }
 
+// One step of a fused stage: outputs `start`, `start + stride`, ... of the NPH branches over history ++ x.  The schemes are tried in
+// turn, each saying whether it served (launched); then the one history update and the buffer swap.
 template <typename T>
 int fused_step(tsdgpu_polyfir *p, const void *dx, void *dy, int stride, int64_t start, int64_t n, int64_t nout, hipStream_t st)
 {
-  if (nout > 0 && p->d_hrev && p->NPH > 1 && stride == 1) {
-    constexpr int RS = 64 / (int) sizeof(T);
+  constexpr int RS = 64 / (int) sizeof(T);       // samples per lane of the direct kernels
+  const T *x = (const T *) dx, *hist = (const T *) p->d_hist[p->cur];
+  T *y = (T *) dy;
+  // upsamplers of rate 2 / 4 with branches of up to 32 taps
+  auto ups_direct = [&]() {
     const int64_t tiles = cdiv(n, (int64_t) 256 * RS);
     const int VECs = 16 / (int) sizeof(T);
     const size_t lds = std::max(((size_t) (256 * RS + p->KPd) / RS + 3) * 80, (size_t) 256 * (RS * p->NPH + VECs) * sizeof(T));
-    if (tiles <= 0x7fffffff) {
-      if (p->NPH == 2) {
-        (void) hipFuncSetAttribute((const void *) ups_direct_kernel<T, RS, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL((ups_direct_kernel<T, RS, 2>), dim3((unsigned) tiles), dim3(256), lds, st, (const T *) dx, (const T *) p->d_hist[p->cur], (T *) dy,
-                           p->d_hrev, p->KPd, p->HW, n, nout);
-      } else {
-        (void) hipFuncSetAttribute((const void *) ups_direct_kernel<T, RS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL((ups_direct_kernel<T, RS, 4>), dim3((unsigned) tiles), dim3(256), lds, st, (const T *) dx, (const T *) p->d_hist[p->cur], (T *) dy,
-                           p->d_hrev, p->KPd, p->HW, n, nout);
-      }
-      TSD_HIP(hipGetLastError());
-      nout = 0;
-    }
-  }
-  if (nout > 0 && p->d_hrev && p->NPH == 1) {
-    constexpr int RS = 64 / (int) sizeof(T);
+    if (!(p->d_hrev && p->NPH > 1 && stride == 1) || tiles > 0x7fffffff) return false;
+    int_switch<2, 4>(p->NPH, [&](auto nph) {
+      hipLaunchKernelGGL((ups_direct_kernel<T, RS, decltype(nph)::value>), dim3((unsigned) tiles), dim3(256), lds, st, x, hist, y, p->d_hrev, p->KPd,
+                         p->HW, n, nout);
+    });
+    return true;
+  };
+  // decimators of rate 2 / 4 / 8 up to 64 taps
+  auto decim_direct = [&]() {
     const int64_t tiles = cdiv(nout, (int64_t) 256 * RS / stride);
     const size_t lds = ((size_t) (256 * RS + p->KPd) / RS + 3) * 80;
-    if (tiles <= 0x7fffffff) {
-#define DD_LAUNCH(D) hipLaunchKernelGGL((decim_direct_kernel<T, RS, D>), dim3((unsigned) tiles), dim3(256), lds, st, (const T *) dx,     \
-                                        (const T *) p->d_hist[p->cur], (T *) dy, p->d_hrev, p->KPd, (int) start, p->HW, n, nout)
-      if (stride == 2) DD_LAUNCH(2); else if (stride == 4) DD_LAUNCH(4); else DD_LAUNCH(8);
-#undef DD_LAUNCH
-      TSD_HIP(hipGetLastError());
-      nout = 0;                                  // (served; the history update below still runs)
-    }
-  }
-  static const bool sans_rangs = dev_switch("POLY_NO_ROWS") != nullptr;
-  if (nout > 0 && !sans_rangs && p->NPH == 1 && stride >= 2 && stride <= PF_ROWS_MAXR && p->W >= 32) {
-    // decimators of small rate and at least 32 taps: polyphase rows (decim_rows_kernel).  (Shorter filters are bound by the
-    // staging, which the phase-major scatter makes dearer: 15 taps at R = 2, 2^26 samples: 0.22 against 0.18 ms.)
+    if (!(p->d_hrev && p->NPH == 1) || tiles > 0x7fffffff) return false;
+    int_switch<2, 4, 8>(stride, [&](auto d) {
+      hipLaunchKernelGGL((decim_direct_kernel<T, RS, decltype(d)::value>), dim3((unsigned) tiles), dim3(256), lds, st, x, hist, y, p->d_hrev, p->KPd,
+                         (int) start, p->HW, n, nout);
+    });
+    return true;
+  };
+  // decimators of small rate and at least 32 taps: polyphase rows (decim_rows_kernel).  (Shorter filters are bound by the
+  // staging, which the phase-major scatter makes dearer: 15 taps at R = 2, 2^26 samples: 0.22 against 0.18 ms.)
+  auto decim_rows = [&]() {
+    if (dev_switch("POLY_NO_ROWS") || !(p->NPH == 1 && stride >= 2 && stride <= PF_ROWS_MAXR && p->W >= 32)) return false;
     const int Lr = ((p->W + stride - 1) / stride + 1 + 3) / 4 * 4, pitch = p->TO + Lr + 4;
     const size_t lds = (size_t) stride * Lr * sizeof(float) + 2 * PF_ROWS_MAXR * sizeof(int) + (size_t) stride * pitch * sizeof(T);
-    if (lds <= 150 * 1024) {
-      (void) hipFuncSetAttribute((const void *) decim_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL(decim_rows_kernel<T>, dim3((unsigned) cdiv(nout, p->TO)), dim3(256), lds, st, (const T *) dx, (const T *) p->d_hist[p->cur],
-                         (T *) dy, p->d_g, stride, p->W, start, p->HW, n, nout, p->TO, Lr, pitch);
-      TSD_HIP(hipGetLastError());
-      nout = 0;                                  // (served; the history update below still runs)
-    }
-  }
-  if (nout > 0) {
+    if (lds > 150 * 1024) return false;
+    (void) hipFuncSetAttribute((const void *) decim_rows_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(decim_rows_kernel<T>, dim3((unsigned) cdiv(nout, p->TO)), dim3(256), lds, st, x, hist, y, p->d_g, stride, p->W, start, p->HW, n, nout,
+                       p->TO, Lr, pitch);
+    return true;
+  };
+  // every other stage: outputs oldest first from the staged span
+  auto oldest_first = [&]() {
     const int64_t span = (int64_t) (p->TO / p->NPH + 1) * stride + p->W;
     const size_t lds = (size_t) ((p->NPH * p->W + 3) & ~3) * sizeof(float) + (size_t) span * sizeof(T);
-    hipLaunchKernelGGL(polyfir_fused_kernel<T>, dim3((unsigned) cdiv(nout, p->TO)), dim3(256), lds, st, (const T *) dx,
-                       (const T *) p->d_hist[p->cur], (T *) dy, p->d_g, p->NPH, p->W, stride, start, p->HW, n, nout, p->TO);
+    hipLaunchKernelGGL(polyfir_fused_kernel<T>, dim3((unsigned) cdiv(nout, p->TO)), dim3(256), lds, st, x, hist, y, p->d_g, p->NPH, p->W, stride, start,
+                       p->HW, n, nout, p->TO);
+    return true;
+  };
+  if (nout > 0) {
+    (void) (ups_direct() || decim_direct() || decim_rows() || oldest_first());
     TSD_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(pf_hist_update_kernel<T>, dim3((unsigned) cdiv(p->HW, 64)), dim3(64), 0, st, (const T *) dx,
-                     (const T *) p->d_hist[p->cur], (T *) p->d_hist[p->cur ^ 1], p->HW, n);
+  hipLaunchKernelGGL(pf_hist_update_kernel<T>, dim3((unsigned) cdiv(p->HW, 64)), dim3(64), 0, st, x, hist, (T *) p->d_hist[p->cur ^ 1], p->HW, n);
   TSD_HIP(hipGetLastError());
   p->cur ^= 1;
   return TSDGPU_OK;
@@ -875,47 +876,28 @@ int tsdgpu_polyfir_step(tsdgpu_polyfir *p, const void *x, int64_t n, void *y, in
   if (rc) return rc;
   rc = stage_out(y, (size_t) nout * sz, p->out_stage, &dy, &staged);
   if (rc) return rc;
-  const bool cplx = p->data_type == TSDGPU_C64;
-  if (p->kind == TSDGPU_POLY_PICK) {
-    // Decimateur: picks x[cnt], x[cnt+R], ...; new cnt = (first index >= n) - n
-    rc = cplx ? launch_pick<float2>(dx, dy, p->cnt, p->R, nout, st) : launch_pick<float>(dx, dy, p->cnt, p->R, nout, st);
-    if (rc) return rc;
-    p->cnt = (int) (p->cnt + nout * p->R - n);
-  } else if (p->fused && p->kind == TSDGPU_POLY_UPS) {
-    // output n*R + i = phase i of input n: group = input index, newest sample = that input
-    rc = cplx ? fused_step<float2>(p, dx, dy, 1, 0, n, nout, st) : fused_step<float>(p, dx, dy, 1, 0, n, nout, st);
-    if (rc) return rc;
-  } else if (p->fused) {
-    // kept outputs sit at local inputs R-1-cnt, then every R
-    const int64_t start = p->R - 1 - p->cnt;
-    rc = cplx ? fused_step<float2>(p, dx, dy, p->R, start, n, nout, st) : fused_step<float>(p, dx, dy, p->R, start, n, nout, st);
-    if (rc) return rc;
-    p->cnt = (int) ((p->cnt + n) % p->R);
-  } else if (p->kind == TSDGPU_POLY_UPS) {
-    rc = p->z.reserve((size_t) n * sz);
-    if (rc) return rc;
-    for (int i = 0; i < p->R; i++) {
-      rc = tsdgpu_fir_step(p->fir[(size_t) i], dx, p->z.p, n, stream);
-      if (rc) return rc;
-      if (cplx)
-        hipLaunchKernelGGL(interleave_kernel<float2>, dim3((unsigned) cdiv(n, 256)), dim3(256), 0, st,
-                           (const float2 *) p->z.p, (float2 *) dy, p->R, i, n);
-      else
-        hipLaunchKernelGGL(interleave_kernel<float>, dim3((unsigned) cdiv(n, 256)), dim3(256), 0, st,
-                           (const float *) p->z.p, (float *) dy, p->R, i, n);
+  const bool ups = p->kind == TSDGPU_POLY_UPS, pick = p->kind == TSDGPU_POLY_PICK;
+  // first output's local input index, and the counter after the call.  Decimateur picks x[cnt], x[cnt + R], ...: the new cnt is
+  // (first index >= n) - n; the decimating filters keep the outputs where the counter wraps: R - 1 - cnt, then every R; an
+  // upsampler's output n R + i is phase i of input n
+  const int64_t start = pick ? p->cnt : ups ? 0 : p->R - 1 - p->cnt;
+  const int cnt_next = pick ? (int) (p->cnt + nout * p->R - n) : ups ? p->cnt : (int) ((p->cnt + n) % p->R);
+  rc = type_switch(p->data_type, [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (pick) return launch_pick<T>(dx, dy, start, p->R, nout, st);
+    if (p->fused) return fused_step<T>(p, dx, dy, ups ? 1 : p->R, start, n, nout, st);
+    // the composition: full-rate FIRs, then the interleave (R upsampler branches) or the pick
+    if (const int e = p->z.reserve((size_t) n * sz)) return e;
+    for (int i = 0; i < (ups ? p->R : 1); i++) {
+      if (const int e = tsdgpu_fir_step(p->fir[(size_t) i], dx, p->z.p, n, stream)) return e;
+      if (!ups) return launch_pick<T>(p->z.p, dy, start, p->R, nout, st);
+      hipLaunchKernelGGL(interleave_kernel<T>, dim3((unsigned) cdiv(n, 256)), dim3(256), 0, st, (const T *) p->z.p, (T *) dy, p->R, i, n);
       TSD_HIP(hipGetLastError());
     }
-  } else {
-    rc = p->z.reserve((size_t) n * sz);
-    if (rc) return rc;
-    rc = tsdgpu_fir_step(p->fir[0], dx, p->z.p, n, stream);
-    if (rc) return rc;
-    // outputs at stream inputs where the counter wraps: local index R-1-cnt, then every R
-    const int64_t start = p->R - 1 - p->cnt;
-    rc = cplx ? launch_pick<float2>(p->z.p, dy, start, p->R, nout, st) : launch_pick<float>(p->z.p, dy, start, p->R, nout, st);
-    if (rc) return rc;
-    p->cnt = (int) ((p->cnt + n) % p->R);
-  }
+    return TSDGPU_OK;
+  });
+  if (rc) return rc;
+  p->cnt = cnt_next;
   if (n_out) *n_out = nout;
   return finish_out(y, (size_t) nout * sz, dy, staged, st);
 }

@@ -11,21 +11,17 @@
 // are an index/permute result and are matched BIT-EXACTLY (same float additions, in the same
 // order, on host and device).
 //
-// The recurrence is sequential, so it is cut with checkpoints: the host simulates it once per
-// handle (lazily, only as far as the stream has advanced), records (phase, outputs so far)
-// every 8 inputs and runs Brent's cycle detection on the phase at input boundaries -- the
-// state space is finite, so the sequence becomes periodic (ratio 160/147: period 3 853 516
-// inputs <-> 4 194 303 outputs) and from then on any stream position is a table lookup.
+// The recurrence is sequential, so it is cut with checkpoints: the host simulates it once per ratio (rs_schedule.hpp: a
+// checkpoint every 8 inputs, the cycle of the phase sequence), and any stream position is a table lookup.
 // On the device every lane restarts from the checkpoint at or below its 8-input segment,
 // replays at most 15+8 inputs, and writes one (input, column) record per output into LDS;
 // then the workgroup evaluates all outputs of the tile in parallel (15 taps x window from
 // LDS) and stores them coalesced.  HBM traffic: 8 B in + 8*ratio B out per complex sample.
 #include "common.hpp"
+#include "rs_schedule.hpp"
 #include <cmath>
 #include <cstdlib>
-#include <map>
 #include <memory>
-#include <mutex>
 
 namespace tsdgpu {
 
@@ -33,7 +29,6 @@ constexpr int RS_WAVES = 8;                     // waves per workgroup; each wav
 constexpr int RS_THREADS = 64 * RS_WAVES;
 constexpr int RS_SEG = 8;                       // inputs per lane
 constexpr int RS_TI = 64 * RS_SEG;              // inputs per (wave) tile: 512
-constexpr int RS_CK = 8;                        // checkpoint spacing (inputs)
 
 struct RsParams {
   int64_t pos;        // absolute index of x[0]
@@ -50,28 +45,13 @@ struct RsParams {
   float inv_den[32];  // Lagrange: 1 / prod_{k != j} (j - k)
 };
 
-struct RsCk { uint32_t phase_bits; uint32_t cum; };
 constexpr int RS_KMAX = 256;                   // longest interpolator (taps); LUTs beyond RS_LUT_LDS_BYTES stay in global memory
 constexpr int RS_LUT_LDS_BYTES = 48 * 1024;      // tables up to this size leave room for RS_WAVES waves per workgroup
 constexpr size_t RS_LDS_LIMIT = 158 * 1024;
-__host__ __device__ inline int rs_tile_elems(int K) { return RS_TI + (K <= 32 ? 32 : (K + 31) / 32 * 32) + 2; }   // cum = outputs before this input (canonical index space)
+__host__ __device__ inline int rs_tile_elems(int K) { return RS_TI + (K <= 32 ? 32 : (K + 31) / 32 * 32) + 2; }
 
-__host__ __device__ inline float bits2f(uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __uint_as_float(b);
-#else
-  float f; memcpy(&f, &b, 4); return f;
-#endif
-}
-__host__ __device__ inline uint32_t f2bits(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __float_as_uint(f);
-#else
-  uint32_t b; memcpy(&b, &f, 4); return b;
-#endif
-}
+// (the device forms; the host's are rs_schedule.hpp's)
+__device__ inline float bits2f(uint32_t b) { return __uint_as_float(b); }
 
 __device__ __forceinline__ float zero_of(float) { return 0.f; }
 __device__ __forceinline__ float2 zero_of(float2) { return make_float2(0.f, 0.f); }
@@ -109,16 +89,14 @@ __device__ __forceinline__ void rs_wrap(int64_t &ic, int64_t &q, int64_t mu, int
   }
 }
 
-// KT = 15: the filtre_reechan interpolator -- taps padded to 16 and read as four ds_read_b128
-// from LUT rows of pitch 20 floats (80 B: 16-B aligned, and 5 mod 16 in 16-B units, so the
-// rows selected by 16 lanes whose columns step regularly fall on distinct bank groups).
-// KT = 0: generic K <= 32, scalar tap reads at an odd pitch.
+// The generic kernel: any K <= RS_KMAX, table-driven or analytic; the table rows are read 16 B at a time at a pitch of an odd
+// number of 16-B units.
 //
 // Work decomposition: the workgroup (8 waves) shares the LUT in LDS; every WAVE owns its own
 // 512-input tiles (64 lanes x 8 inputs) with a private sample window and record list, so the
 // tile loop contains no workgroup barrier at all -- waves drift freely and hide each other's
 // latencies.  The next tile's samples and checkpoint are prefetched into registers.
-template <typename T, int KT>
+template <typename T>
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const T *__restrict__ x, const T *__restrict__ hist,
                                                               T *__restrict__ y, const float *__restrict__ lut,
                                                               const RsCk *__restrict__ ck, RsParams P, int ntiles,
@@ -137,8 +115,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const T *__restric
     return;
   }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int K = KT > 0 ? KT : P.K;
-  const int lstride = KT == 15 ? 20 : P.lstride;
+  const int K = P.K;
+  const int lstride = P.lstride;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   float *lut_s = reinterpret_cast<float *>(smem_raw);                       // (nph+1) x lstride, 16-B aligned
   char *wbase = reinterpret_cast<char *>(lut_s + (P.lut_in_lds ? ((P.nph + 1) * lstride + 3) / 4 * 4 : 4));
@@ -156,8 +134,6 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const T *__restric
   }
   const float *lutp = P.lut_in_lds ? lut_s : lut;
   const int lrow = P.lut_in_lds ? lstride : P.gl;         // both multiples of 4: rows are read 16 B at a time
-  if (KT == 15)
-    for (int c = threadIdx.x; c <= P.nph; c += NT) lut_s[c * lstride + 15] = 0.f;   // 16th tap
   __syncthreads();
 
   auto wave_sync = []() {
@@ -276,16 +252,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const T *__restric
       const T *w = tile + (r >> 13);                         // window: x[i-K+1 .. i], oldest first
       const float *h = lutp + (r & 8191u) * lrow;
       T acc = zero_of(T{});
-      if (KT == 15) {
-        float hh[16];
-#pragma unroll
-        for (int k4 = 0; k4 < 4; k4++) {
-          const float4 q4 = *reinterpret_cast<const float4 *>(h + 4 * k4);
-          hh[4 * k4] = q4.x; hh[4 * k4 + 1] = q4.y; hh[4 * k4 + 2] = q4.z; hh[4 * k4 + 3] = q4.w;
-        }
-#pragma unroll
-        for (int k = 0; k < 15; k++) acc = tap_mac(acc, hh[k], w[k]);   // filtrage.hpp:1877-1879 order
-      } else if (P.mode == 0) {
+      if (P.mode == 0) {
+        // (taps 0 .. K - 1 in the order of filtrage.hpp:1877-1879)
         // taps 16 B at a time (a row per lane: scalar reads cost one cache line or LDS access per tap)
         const int K4 = K & ~3;
 #pragma unroll 4
@@ -591,6 +559,37 @@ struct RsDyn {
   unsigned *ctr;
   unsigned base, Q;
   int NC;            // 0: static partition (tile = wave + k * waves)
+};
+// The dynamic tile hand-out of resample15s_kernel (RsDyn) on the host, after fft.hip's TileCounter: the device counters are never
+// reset; their value before the next launch is tracked here and goes into each launch as its base.  begin() fills the launch
+// argument for NC counters (0: the static partition), zeroing them when the count changes or a launch that used them failed;
+// commit() advances the base once the launch has been accepted.
+struct RsCounters {
+  unsigned *d = nullptr;      // RS_MAX_CTR counters on 128-B lines, behind the histories in the handle's allocation
+  unsigned base = 0;
+  int nc = 0;                 // the count the device values stand for; 0: zero them before the next use
+  unsigned add = 0;           // between begin() and commit(): what this launch advances every counter by
+
+  int begin(int NC, int64_t tiles, int64_t grid, int NW, hipStream_t st, RsDyn *dyn)
+  {
+    add = 0;
+    if (NC > 0 && NC != nc) {
+      TSD_HIP(hipMemsetAsync(d, 0, (size_t) RS_MAX_CTR * 128, st));
+      base = 0;
+      nc = NC;
+    }
+    *dyn = RsDyn{d, base, 0u, NC};
+    if (NC > 0) {
+      dyn->Q = (unsigned) cdiv(tiles, NC);
+      add = dyn->Q + (unsigned) (grid / NC * NW);
+    }
+    return TSDGPU_OK;
+  }
+  void commit(bool launched)
+  {
+    if (launched) base += add;
+    else if (add) nc = 0;     // (device counters and host base may have parted)
+  }
 };
 constexpr int RS15_TILE_PAD = (RS_TI + 16) + (RS_TI + 16) / 8 + 2;      // padded sample slots per wave (lane stride 9: sample s at s + (s >> 3))
 
@@ -968,233 +967,71 @@ __global__ __launch_bounds__(1024) void resample15s_kernel(const T *__restrict__
 
 using namespace tsdgpu;
 
-// The schedule of the float32 phase recurrence depends on the increment alone: it is simulated
-// ONCE per ratio and per process -- checkpoints every RS_CK inputs up to the end of the first
-// period -- and shared by all the handles of that ratio (a rééchan()-style one-shot call creates
-// a handle per call: without the cache every call replayed up to 8 M sequential steps, tens of ms).
-struct RsSched {
-  std::mutex mtx;
-  std::vector<RsCk> ck;       // checkpoints every RS_CK inputs of the canonical sequence
-  int64_t sim_i = 0;          // inputs simulated so far (canonical)
-  float sim_phase = 0.f;
-  int64_t sim_cum = 0;
-  // Brent cycle detection on the phase at input boundaries
-  uint32_t tort_bits = 0;
-  int64_t brent_power = 1, brent_lam = 0;
-  bool cyc = false;
-  int64_t mu = 0, lambda = 0, opp = 0;
-  // the table grows 8 B per RS_CK inputs until the period is found, and counts outputs in 32 bits: a
-  // recurrence whose period were not found within RS_SIM_MAX inputs is refused instead of growing on
-  bool failed = false;
-};
-constexpr int64_t RS_SIM_MAX = (int64_t) 1 << 29;      // inputs (a 256 MiB table); 160/147 needs 8 M
-static std::shared_ptr<RsSched> sched_for(float inc)
-{
-  static std::mutex m;
-  static std::map<uint32_t, std::shared_ptr<RsSched>> cache;
-  std::lock_guard<std::mutex> lock(m);
-  uint32_t key;
-  memcpy(&key, &inc, 4);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  if (cache.size() >= 32) cache.erase(cache.begin());        // (handles keep their own reference)
-  auto sp = std::make_shared<RsSched>();
-  cache[key] = sp;
-  return sp;
-}
-
 struct tsdgpu_resampler {
   int data_type = 0, K = 0, nph = 0, lstride = 0, gl = 0, mode = 0;
   float ratio = 1.f, inc = 1.f;
   float inv_den[32] = {0};
-  float *d_lut = nullptr;
+  float *d_lut = nullptr;      // ONE allocation: table | history A | history B | counters (DevImage)
   void *d_hist[2] = {nullptr, nullptr};
   bool hist_zero = true;       // the window history is all zeros (start, reset, seek without samples): the kernels get a null pointer instead of a cleared buffer
   int cur = 0;
   // stream position
   int64_t pos = 0, cum_pos = 0;
-  // host schedule (shared by every handle of the same ratio, see RsSched)
-  std::shared_ptr<RsSched> sch;
-  std::vector<RsCk> &ck;
-  int64_t &sim_i;
-  float &sim_phase;
-  int64_t &sim_cum;
-  uint32_t &tort_bits;
-  int64_t &brent_power, &brent_lam;
-  bool &cyc;
-  int64_t &mu, &lambda, &opp;
-  explicit tsdgpu_resampler(std::shared_ptr<RsSched> s_)
-      : sch(std::move(s_)), ck(sch->ck), sim_i(sch->sim_i), sim_phase(sch->sim_phase), sim_cum(sch->sim_cum),
-        tort_bits(sch->tort_bits), brent_power(sch->brent_power), brent_lam(sch->brent_lam), cyc(sch->cyc), mu(sch->mu),
-        lambda(sch->lambda), opp(sch->opp) {}
+  std::shared_ptr<RsSchedule> sch;      // host schedule, shared by every handle of the same ratio (rs_schedule.hpp)
   RsCk *d_ck = nullptr;
   uint32_t *d_ph = nullptr;     // the phases alone (resample15s_kernel: 4 B per checkpoint), behind d_ck in its allocation
   size_t d_ck_cap = 0, d_ck_n = 0;
   DevBuf in_stage, out_stage;
-  // work counters of the fused kernel's dynamic tile hand-out (RsDyn), behind the histories in d_lut's allocation
-  unsigned *d_ctr = nullptr;
-  unsigned ctr_base = 0;
-  int ctr_nc = 0;
+  RsCounters ctr;
 };
 
 namespace {
 
-inline void sim_one(float &phase, int64_t &cum, float inc)
+int rs_no_period(const char *entry, const tsdgpu_resampler *r)
 {
-  // plain binary32 adds (SSE scalar ops; this file is compiled without fast-math or contraction)
-  float p = phase;
-  while (p < 1.f) { p = p + inc; cum++; }
-  p = p - 1.f;
-  phase = p;
+  return set_err(TSDGPU_ERR_UNSUPPORTED, "%s: the float32 phase recurrence of ratio %g shows no period within 2^29 inputs", entry,
+                 (double) r->ratio);
 }
 
-// state (phase, outputs before) at canonical input index ic, ic <= sim_i
-void state_at_canonical(const tsdgpu_resampler *r, int64_t ic, float *phase, int64_t *cum)
-{
-  const RsCk &c = r->ck[(size_t) (ic / RS_CK)];
-  float p = bits2f(c.phase_bits);
-  int64_t cu = c.cum;
-  for (int64_t s = ic % RS_CK; s > 0; s--) sim_one(p, cu, r->inc);
-  *phase = p;
-  *cum = cu;
-}
-
-// advance the host simulation until it covers canonical index `upto` or the cycle is known
-void extend(tsdgpu_resampler *r, int64_t upto)
-{
-  while (!r->cyc && !r->sch->failed && r->sim_i < upto + RS_CK) {
-    if (r->sim_i >= RS_SIM_MAX || r->sim_cum >= (int64_t) 0xFFFF0000ll) {
-      r->sch->failed = true;
-      return;
-    }
-    if (r->sim_i % RS_CK == 0) r->ck.push_back(RsCk{f2bits(r->sim_phase), (uint32_t) r->sim_cum});
-    // Brent: compare the state at this input boundary with the tortoise
-    const uint32_t bits = f2bits(r->sim_phase);
-    if (r->sim_i == 0) {
-      r->tort_bits = bits;
-    } else {
-      r->brent_lam++;
-      if (bits == r->tort_bits) {
-        r->lambda = r->brent_lam;
-        // mu = first index whose state recurs lambda inputs later
-        float pa = 0.f, pb;
-        int64_t ca = 0, cb;
-        state_at_canonical(r, r->lambda, &pb, &cb);
-        int64_t m = 0;
-        while (f2bits(pa) != f2bits(pb)) {
-          sim_one(pa, ca, r->inc);
-          sim_one(pb, cb, r->inc);
-          m++;
-        }
-        r->mu = m;
-        r->opp = cb - ca;
-        r->cyc = true;
-        // make sure the table covers [0, mu + lambda + RS_CK)
-        while (r->sim_i < r->mu + r->lambda + 2 * RS_CK) {
-          sim_one(r->sim_phase, r->sim_cum, r->inc);
-          r->sim_i++;
-          if (r->sim_i % RS_CK == 0) r->ck.push_back(RsCk{f2bits(r->sim_phase), (uint32_t) r->sim_cum});
-        }
-        return;
-      }
-      if (r->brent_lam == r->brent_power) {
-        r->tort_bits = bits;
-        r->brent_power *= 2;
-        r->brent_lam = 0;
-      }
-    }
-    sim_one(r->sim_phase, r->sim_cum, r->inc);
-    r->sim_i++;
-  }
-}
-
-// outputs emitted before absolute input index i (and the phase there)
-void state_at(tsdgpu_resampler *r, int64_t i, float *phase, int64_t *cum)
-{
-  extend(r, i);
-  int64_t ic = i, q = 0;
-  if (r->cyc && i >= r->mu + r->lambda) {
-    const int64_t d = i - r->mu;
-    q = d / r->lambda;
-    ic = r->mu + d % r->lambda;
-  }
-  state_at_canonical(r, ic, phase, cum);
-  *cum += q * r->opp;
-}
-
+// the device copy of the schedule table follows the host's
 int sync_table(tsdgpu_resampler *r, hipStream_t st)
 {
-  if (r->d_ck_n == r->ck.size()) return TSDGPU_OK;
-  if (r->ck.size() > r->d_ck_cap) {
-    RsCk *nd = nullptr;
-    const size_t cap = r->ck.size() + r->ck.size() / 2 + 1024;
-    if (hipMalloc((void **) &nd, cap * (sizeof(RsCk) + sizeof(uint32_t))) != hipSuccess)
-      return set_err(TSDGPU_ERR_ALLOC, "resampler: schedule table alloc failed");
-    TSD_HIP(hipStreamSynchronize(st));
-    if (r->d_ck) (void) hipFree(r->d_ck);
-    r->d_ck = nd;
-    r->d_ph = reinterpret_cast<uint32_t *>(nd + cap);
-    r->d_ck_cap = cap;
-    r->d_ck_n = 0;
-  }
-  const size_t fresh = r->ck.size() - r->d_ck_n;
-  std::vector<uint32_t> phases(fresh);
-  for (size_t i = 0; i < fresh; i++) phases[i] = r->ck[r->d_ck_n + i].phase_bits;
-  TSD_HIP(hipMemcpyAsync(r->d_ck + r->d_ck_n, r->ck.data() + r->d_ck_n, fresh * sizeof(RsCk), hipMemcpyHostToDevice, st));
-  TSD_HIP(hipMemcpyAsync(r->d_ph + r->d_ck_n, phases.data(), fresh * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  TSD_HIP(hipStreamSynchronize(st));    // the vectors may grow (reallocate) / go away before the copies have run
-  r->d_ck_n = r->ck.size();
-  return TSDGPU_OK;
+  return r->sch->checkpoints_from(0, [&](const RsCk *ck, size_t n) -> int {
+    if (r->d_ck_n == n) return TSDGPU_OK;
+    if (n > r->d_ck_cap) {
+      RsCk *nd = nullptr;
+      const size_t cap = n + n / 2 + 1024;
+      if (hipMalloc((void **) &nd, cap * (sizeof(RsCk) + sizeof(uint32_t))) != hipSuccess)
+        return set_err(TSDGPU_ERR_ALLOC, "resampler: schedule table alloc failed");
+      TSD_HIP(hipStreamSynchronize(st));
+      if (r->d_ck) (void) hipFree(r->d_ck);
+      r->d_ck = nd;
+      r->d_ph = reinterpret_cast<uint32_t *>(nd + cap);
+      r->d_ck_cap = cap;
+      r->d_ck_n = 0;
+    }
+    const size_t fresh = n - r->d_ck_n;
+    std::vector<uint32_t> phases(fresh);
+    for (size_t i = 0; i < fresh; i++) phases[i] = ck[r->d_ck_n + i].phase_bits;
+    TSD_HIP(hipMemcpyAsync(r->d_ck + r->d_ck_n, ck + r->d_ck_n, fresh * sizeof(RsCk), hipMemcpyHostToDevice, st));
+    TSD_HIP(hipMemcpyAsync(r->d_ph + r->d_ck_n, phases.data(), fresh * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    TSD_HIP(hipStreamSynchronize(st));    // the vectors may grow (reallocate) / go away before the copies have run
+    r->d_ck_n = n;
+    return TSDGPU_OK;
+  });
 }
 
-}  // namespace
-
-// LDS bytes per workgroup of the generic kernel for this handle (the arithmetic of tsdgpu_resampler_step):
-// checked at creation so that a configuration no step could launch -- a large ratio with wide complex
-// tiles -- is refused there instead of failing at every step
-// Geometry of the generic kernel for this handle: is the table staged in LDS, and how many waves share it.  A table of up to
-// 48 KiB leaves room for RS_WAVES waves; a LONG interpolator's table (itrp_sinc{127, 256, ...} of the reference's test_ra_unit:
-// 257 rows of 132 floats = 133 KiB) is staged too when at least two waves' tiles still fit beside it -- read through L2
-// instead (a row per lane per tap quadruple: 64 cache lines per wave instruction) it cost 5.7 ms per 2^26 inputs.
-struct RsGeom {
-  bool lut_in_lds;
-  int waves;
-  size_t lds;
-};
-static RsGeom rs_geometry(const tsdgpu_resampler *r, int mode)
-{
-  const size_t sz = dtype_size(r->data_type);
-  const int rec_cap = ((int) ((double) RS_TI * (double) r->ratio * 1.0001) + 32 + 3) / 4 * 4;
-  const size_t wbytes = ((size_t) rs_tile_elems(r->K) * sz + (size_t) rec_cap * (mode ? 8 : 4) + 15) / 16 * 16;
-  const int lstride = r->K == 15 ? 20 : r->lstride;
-  const size_t lut = ((size_t) (r->nph + 1) * lstride + 4) * 4;
-  RsGeom g;
-  g.lut_in_lds = lut - 16 <= (size_t) RS_LUT_LDS_BYTES;
-  g.waves = RS_WAVES;
-  if (!g.lut_in_lds && mode == 0 && lut + 64 + 2 * wbytes <= RS_LDS_LIMIT) {
-    g.lut_in_lds = true;
-    g.waves = (int) std::min<size_t>(RS_WAVES, (RS_LDS_LIMIT - lut - 64) / wbytes);
-  }
-  g.lds = (g.lut_in_lds ? lut : 32) + (size_t) g.waves * wbytes + 64;
-  return g;
-}
-static size_t rs_lds_need(const tsdgpu_resampler *r, int mode) { return rs_geometry(r, mode).lds; }
 // geometry of resample_long_kernel, or waves = 0 when the handle does not qualify (table-driven, 24 taps and more, at most two
 // outputs per input, table + one wave within the LDS); TSDGPU_RS_LONG=0 keeps such handles on resample_kernel
-struct RsLongGeom {
-  int waves, cap2, kp, nphase;
-  size_t lds;
-};
-static RsLongGeom rs_long_geometry(const tsdgpu_resampler *r)
+struct RsLongGeom { int waves, cap2, kp, nphase; size_t lds; };
+RsLongGeom rs_long_geometry(const tsdgpu_resampler *r)
 {
   RsLongGeom g = {0, 0, 0, 0, 0};
   // (read per call: the tests flip them between handles)
-  const char *e_off = dev_switch("RS_LONG"), *e_kmin = dev_switch("RS_LONG_KMIN"), *e_w = dev_switch("RS_LONG_WAVES"),
-             *e_ph = dev_switch("RS_LONG_PHASES");
-  const bool off = e_off && atoi(e_off) == 0;
-  const int kmin = e_kmin ? atoi(e_kmin) : 24;
-  const int want = e_w ? atoi(e_w) : 8;                      // waves per workgroup aimed at
-  const int force_ph = e_ph ? atoi(e_ph) : 0;
+  const bool off = dev_switch_int("RS_LONG", 1) == 0;
+  const int kmin = dev_switch_int("RS_LONG_KMIN", 24);
+  const int want = dev_switch_int("RS_LONG_WAVES", 8);       // waves per workgroup aimed at
+  const int force_ph = dev_switch_int("RS_LONG_PHASES", 0);
   if (off || r->mode != 0 || r->K < kmin || !(r->inc >= 0.5f)) return g;
   const size_t sz = dtype_size(r->data_type);
   g.cap2 = r->ratio > 1.f ? ((int) ((double) RS_TI * ((double) r->ratio - 1.0) * 1.0001) + 40 + 1) / 2 * 2 : 8;
@@ -1202,7 +1039,6 @@ static RsLongGeom rs_long_geometry(const tsdgpu_resampler *r)
   // as few tap phases as leave room for `want` waves (at most 8: the kernel's bound); a table too large for that takes the phase
   // count that leaves the most waves, down to one
   const int kc = (r->K + RSL_CH - 1) / RSL_CH;               // chunks of taps
-  int best_w = 0;
   for (int nph = 1; nph <= kc; nph++) {
     if (force_ph > 0 && nph != std::min(force_ph, kc)) continue;
     const int kp = (kc + nph - 1) / nph * RSL_CH;
@@ -1210,17 +1046,92 @@ static RsLongGeom rs_long_geometry(const tsdgpu_resampler *r)
     const size_t lut = (size_t) (r->nph + 1) * (kp + 4) * 4;
     if (lut + wbytes + 64 > RS_LDS_LIMIT) continue;
     const int w = (int) std::min<size_t>(8, (RS_LDS_LIMIT - lut - 64) / wbytes);
-    if (w > best_w) {
-      best_w = w;
-      g.waves = w;
-      g.kp = kp;
-      g.nphase = nph;
-      g.lds = lut + (size_t) w * wbytes + 64;
-    }
+    if (w > g.waves) g = RsLongGeom{w, g.cap2, kp, nph, lut + (size_t) w * wbytes + 64};
     if (w >= std::min(want, 8)) break;
   }
   return g;
 }
+
+// The plan of one step: which of the three kernels serves `tiles` tiles of this handle on `st`, and its launch geometry.
+//  - resample15s_kernel: K = 15 at a ratio of at most 2 (at most two outputs per input), as many waves per workgroup as its LDS
+//    allows; TSDGPU_RS15=0 sends the interpolator through the kernels of the other lengths (parity tests).  Its tiles are handed
+//    out dynamically over NC counters (TSDGPU_RS_DYN, 0: static partition) from TSDGPU_RS_DYN_MIN tiles per wave on, unless `st`
+//    records a graph (the base is a launch argument).
+//  - resample_long_kernel: rs_long_geometry.
+//  - resample_kernel serves everything else, and every handle must fit it (gen_lds: what it needs; the creation refuses a
+//    configuration beyond the LDS -- a large ratio with wide complex tiles -- instead of every step).  Is the table staged in
+//    LDS, and how many waves share it: a table of up to 48 KiB leaves room for RS_WAVES waves; a LONG interpolator's table
+//    (itrp_sinc{127, 256, ...} of the reference's test_ra_unit: 257 rows of 132 floats = 133 KiB) is staged too when at least two
+//    waves' tiles still fit beside it -- read through L2 instead (a row per lane per tap quadruple: 64 cache lines per wave
+//    instruction) it cost 5.7 ms per 2^26 inputs.
+struct RsPlan {
+  enum { K15S, LONG, GENERIC } kernel = GENERIC;
+  int waves = 0;              // per workgroup
+  size_t lds = 0;             // dynamic LDS bytes of the launch
+  int rec_cap = 0;            // output records per wave: outputs are spaced 1/ratio apart in input time (up to float32 rounding of the adds)
+  int64_t grid = 0;           // persistent workgroups (the LUT is staged once per workgroup); the launch adds the one that writes the history
+  int lcap15 = 0, NC = 0;     // K15S: capacity of a wave's list of second outputs, counters of the dynamic hand-out
+  bool lut_in_lds = false;    // resample_kernel: the table is staged in LDS
+  RsLongGeom lg = {0, 0, 0, 0, 0};
+  size_t gen_lds = 0;
+};
+RsPlan rs_plan(const tsdgpu_resampler *r, int64_t tiles, hipStream_t st)
+{
+  RsPlan p;
+  const size_t sz = dtype_size(r->data_type);
+  const double rt = (double) RS_TI * (double) r->ratio * 1.0001;
+  // resample_kernel
+  const int rec_cap = ((int) rt + 32 + 3) / 4 * 4;
+  const size_t wbytes = ((size_t) rs_tile_elems(r->K) * sz + (size_t) rec_cap * (r->mode ? 8 : 4) + 15) / 16 * 16;
+  const size_t lut = ((size_t) (r->nph + 1) * r->lstride + 4) * 4;
+  bool in_lds = lut - 16 <= (size_t) RS_LUT_LDS_BYTES;
+  int waves = RS_WAVES;
+  if (!in_lds && r->mode == 0 && lut + 64 + 2 * wbytes <= RS_LDS_LIMIT) {
+    in_lds = true;
+    waves = (int) std::min<size_t>(RS_WAVES, (RS_LDS_LIMIT - lut - 64) / wbytes);
+  }
+  p.gen_lds = (in_lds ? lut : 32) + (size_t) waves * wbytes + 64;
+  p.lut_in_lds = in_lds;
+  p.rec_cap = rec_cap;
+  if (r->K == 15 && r->mode == 0 && r->inc >= 0.5f && r->nph <= 511 && dev_switch_int("RS15", 1) != 0) {
+    const int rec15 = ((int) rt + 8 + 3) / 4 * 4;
+    const int lcap15 = (int) ((double) RS_TI * std::max(0.0, (double) r->ratio - 1.0) * 1.0001) + 8;
+    const size_t wb15 = ((size_t) (RS15_TILE_PAD + rec15) * sz + (size_t) lcap15 * 4 + RS15S_CKB + 15) / 16 * 16;
+    const size_t lut15 = (size_t) ((r->nph + 1) * 20 + 4) * 4;
+    const int nw = (int) std::min<size_t>(16, (RS_LDS_LIMIT - lut15 - 64) / wb15);
+    if (nw >= 4) {
+      int NC = dev_switch_int("RS_DYN", 16);
+      if (NC < 0 || NC > RS_MAX_CTR || !r->ctr.d || 256 % (8 * std::max(NC, 1)) != 0) NC = 0;
+      if (tiles < (int64_t) dev_switch_int("RS_DYN_MIN", 4) * 256 * nw || (NC > 0 && stream_is_capturing(st))) NC = 0;
+      p.kernel = RsPlan::K15S, p.waves = nw, p.lds = lut15 + (size_t) nw * wb15 + 64;
+      p.rec_cap = rec15, p.lcap15 = lcap15, p.NC = NC;
+      p.grid = NC > 0 ? 256 : std::min<int64_t>(cdiv(tiles, nw), 256);
+      return p;
+    }
+  }
+  if (p.lg = rs_long_geometry(r); p.lg.waves > 0) {
+    p.kernel = RsPlan::LONG, p.waves = p.lg.waves, p.lds = p.lg.lds;
+    p.grid = std::min<int64_t>(cdiv(tiles, p.waves), 256);
+    return p;
+  }
+  p.waves = waves;
+  p.lds = p.gen_lds;
+  // as many workgroups as stay resident
+  const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (p.lds + 1024)));
+  p.grid = std::min<int64_t>(cdiv(tiles, waves), (int64_t) 256 * per_cu);
+  return p;
+}
+
+RsParams rs_params(const tsdgpu_resampler *r, int64_t n, const RsCycle &cy, const RsPlan &pl)
+{
+  // (in the order of the members)
+  RsParams P = {r->pos, n, (r->pos / RS_TI) * RS_TI, cy.mu, cy.lambda, cy.opp, r->cum_pos, r->inc, r->K, r->nph, r->lstride, pl.rec_cap,
+                pl.lut_in_lds ? 1 : 0, r->mode, r->gl, {0}};
+  memcpy(P.inv_den, r->inv_den, sizeof P.inv_den);
+  return P;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1237,7 +1148,7 @@ int tsdgpu_resampler_create(tsdgpu_resampler **out, int data_type, float ratio, 
                    "ratios into [0.5,2) with half-band stages first)", (double) ratio);
   if (K < 1 || K > RS_KMAX || nphases < 1 || nphases > 8191)
     return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_create: K=%d nphases=%d unsupported (K <= %d, nphases <= 8191)", K, nphases, RS_KMAX);
-  tsdgpu_resampler *r = new tsdgpu_resampler(sched_for(1.f / ratio));
+  tsdgpu_resampler *r = new tsdgpu_resampler();
   r->data_type = data_type;
   r->K = K;
   r->nph = nphases;
@@ -1245,43 +1156,31 @@ int tsdgpu_resampler_create(tsdgpu_resampler **out, int data_type, float ratio, 
   r->lstride = r->gl + (((r->gl / 4) & 1) ? 0 : 4);      // LDS pitch: a multiple of 4 floats with an odd number of 16-B units
   r->ratio = ratio;
   r->inc = 1.f / ratio;                      // ra.cc:29
-  const size_t lut_bytes = (size_t) (nphases + 1) * ((K + 3) / 4 * 4) * sizeof(float);
-  // ONE allocation (the table with its rows padded to 16 bytes, then the two window histories) and ONE upload of its host
-  // image: a one-shot rééchan() pays for every creation (three allocations, a memset, a strided copy, two memsets and a
-  // synchronisation before)
-  const size_t hb = ((size_t) std::max(K - 1, 1) * dtype_size(data_type) + 15) / 16 * 16, lb = (lut_bytes + 15) / 16 * 16;
-  int rc = TSDGPU_OK;
-  const size_t ctr_bytes = (size_t) RS_MAX_CTR * 128;
-  std::vector<char> image(lb + 2 * hb + ctr_bytes, 0);
+  r->sch = RsSchedule::sched_for(r->inc);
+  // the table with its rows padded to 16 bytes, then the two window histories (zeros) and the hand-out counters (zeros)
+  DevImage img;
+  const size_t hb = (size_t) std::max(K - 1, 1) * dtype_size(data_type);
+  const size_t o_lut = img.reserve((size_t) (nphases + 1) * r->gl * sizeof(float)), o_h0 = img.reserve(hb), o_h1 = img.reserve(hb),
+               o_ctr = img.reserve((size_t) RS_MAX_CTR * 128);
   for (int c = 0; c <= nphases; c++)
-    std::memcpy(image.data() + (size_t) c * r->gl * sizeof(float), lut_host + (size_t) c * K, (size_t) K * sizeof(float));
-  if (hipMalloc((void **) &r->d_lut, image.size()) != hipSuccess)
-    rc = set_err(TSDGPU_ERR_HIP, "resampler_create: hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
-  else if (hipMemcpy(r->d_lut, image.data(), image.size(), hipMemcpyHostToDevice) != hipSuccess)
-    rc = set_err(TSDGPU_ERR_HIP, "resampler_create: upload failed: %s", hipGetErrorString(hipGetLastError()));
-  if (!rc) {
-    r->d_hist[0] = (char *) r->d_lut + lb;
-    r->d_hist[1] = (char *) r->d_lut + lb + hb;
-    r->d_ctr = (unsigned *) ((char *) r->d_lut + lb + 2 * hb);      // (lb and hb are multiples of 16 bytes)
-  }
+    std::memcpy(img.at<float>(o_lut) + (size_t) c * r->gl, lut_host + (size_t) c * K, (size_t) K * sizeof(float));
+  int rc = img.upload("resampler_create");
+  r->d_lut = img.dev<float>(o_lut);
   if (rc) {
     tsdgpu_resampler_destroy(r);
     return rc;
   }
-  {
-    const size_t lds = rs_lds_need(r, 0);
-    if (lds > 158 * 1024) {
-      tsdgpu_resampler_destroy(r);
-      return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_create: ratio %g with %d taps on %s data needs %zu bytes of LDS per workgroup (limit 158 KiB): "
-                     "fold the ratio with half-band stages first (filtre_reechan does)", (double) ratio, K, data_type == TSDGPU_C64 ? "complex" : "real", lds);
-    }
+  r->d_hist[0] = img.dev(o_h0);
+  r->d_hist[1] = img.dev(o_h1);
+  r->ctr.d = img.dev<unsigned>(o_ctr);
+  if (const size_t lds = rs_plan(r, 0, nullptr).gen_lds; lds > RS_LDS_LIMIT) {
+    tsdgpu_resampler_destroy(r);
+    return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_create: ratio %g with %d taps on %s data needs %zu bytes of LDS per workgroup (limit 158 KiB): "
+                   "fold the ratio with half-band stages first (filtre_reechan does)", (double) ratio, K, data_type == TSDGPU_C64 ? "complex" : "real", lds);
   }
-  (void) hipFuncSetAttribute((const void *) resample_kernel<float, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) resample_kernel<float2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) resample_long_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) resample_long_kernel<float2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) resample15s_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void) hipFuncSetAttribute((const void *) resample15s_kernel<float2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  for (const void *k : {(const void *) resample_kernel<float>, (const void *) resample_kernel<float2>, (const void *) resample_long_kernel<float>,
+                        (const void *) resample_long_kernel<float2>, (const void *) resample15s_kernel<float>, (const void *) resample15s_kernel<float2>})
+    (void) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void) hipGetLastError();
   *out = r;
   return TSDGPU_OK;
@@ -1298,7 +1197,7 @@ int tsdgpu_resampler_create_analytic(tsdgpu_resampler **out, int data_type, floa
   int rc = tsdgpu_resampler_create(out, data_type, ratio, dummy.data(), K, 1);
   if (rc) return rc;
   (*out)->mode = kind;
-  if (rs_lds_need(*out, kind) > 158 * 1024) {
+  if (rs_plan(*out, 0, nullptr).gen_lds > RS_LDS_LIMIT) {      // (the analytic interpolators keep the phase beside each record)
     tsdgpu_resampler_destroy(*out);
     *out = nullptr;
     return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_create_analytic: ratio %g needs more LDS than a workgroup has: fold the ratio first", (double) ratio);
@@ -1315,15 +1214,12 @@ int tsdgpu_resampler_create_analytic(tsdgpu_resampler **out, int data_type, floa
 int64_t tsdgpu_resampler_out_count(tsdgpu_resampler *r, int64_t n)
 {
   if (!r || n < 0) return -1;
-  float ph;
-  int64_t c;
-  std::lock_guard<std::mutex> lock(r->sch->mtx);
-  state_at(r, r->pos + n, &ph, &c);
-  if (r->sch->failed) {
-    set_err(TSDGPU_ERR_UNSUPPORTED, "resampler: the float32 phase recurrence of ratio %g shows no period within 2^29 inputs", (double) r->ratio);
+  RsState s;
+  if (!r->sch->state_at(r->pos + n, &s)) {
+    rs_no_period("resampler", r);
     return -1;
   }
-  return c - r->cum_pos;
+  return s.cum - r->cum_pos;
 }
 
 int tsdgpu_resampler_step(tsdgpu_resampler *r, const void *x, int64_t n, void *y, int64_t y_capacity, int64_t *n_out,
@@ -1335,37 +1231,32 @@ int tsdgpu_resampler_step(tsdgpu_resampler *r, const void *x, int64_t n, void *y
   if (n == 0) return TSDGPU_OK;
   TSD_CHECK(x != nullptr, "resampler_step: NULL input");
   hipStream_t st = (hipStream_t) stream;
+  const size_t sz = dtype_size(r->data_type);
   // a large HOST vector goes through in chunks: H2D of chunk i+1, the kernel of chunk i and D2H of chunk i-1 overlap
   // (position, window and output offset are carried from chunk to chunk exactly as between two calls)
-  if ((size_t) n * dtype_size(r->data_type) >= PIPE_MIN_BYTES && host_pipe_enabled() && y != nullptr && !is_device_ptr(x) && !is_device_ptr(y)) {
-    const size_t esz = dtype_size(r->data_type);
+  if ((size_t) n * sz >= PIPE_MIN_BYTES && host_pipe_enabled() && y != nullptr && !is_device_ptr(x) && !is_device_ptr(y)) {
     const int64_t total = tsdgpu_resampler_out_count(r, n);
     if (total < 0) return TSDGPU_ERR_INVALID;
     TSD_CHECK(total <= y_capacity, "resampler_step: output needs %lld samples, capacity is %lld", (long long) total, (long long) y_capacity);
-    if (!host_ranges_overlap(x, (size_t) n * esz, y, (size_t) total * esz)) {
+    if (!host_ranges_overlap(x, (size_t) n * sz, y, (size_t) total * sz)) {
       const double ratio = (double) r->ratio;
       return pipelined_host_step_var(
-          x, n, esz, y, esz, n_out, 1, st, [ratio](int64_t c) { return (int64_t) ((double) c * ratio * 1.0001) + 64; },
+          x, n, sz, y, sz, n_out, 1, st, [ratio](int64_t c) { return (int64_t) ((double) c * ratio * 1.0001) + 64; },
           [r](const void *cx, void *cy, int64_t cnt, int64_t cap, int64_t *got, hipStream_t q) {
             return tsdgpu_resampler_step(r, cx, cnt, cy, cap, got, q);
           });
     }
   }
-  float ph_end;
-  int64_t cum_end;
-  // (the schedule is shared between the handles of a ratio: held while this call reads or extends it)
-  std::lock_guard<std::mutex> lock(r->sch->mtx);
-  state_at(r, r->pos + n, &ph_end, &cum_end);
-  if (r->sch->failed)
-    return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_step: the float32 phase recurrence of ratio %g shows no period within 2^29 inputs",
-                   (double) r->ratio);
-  const int64_t nout = cum_end - r->cum_pos;
+  RsState end;
+  if (!r->sch->state_at(r->pos + n, &end)) return rs_no_period("resampler_step", r);
+  const int64_t nout = end.cum - r->cum_pos;
   TSD_CHECK(nout <= y_capacity, "resampler_step: output needs %lld samples, capacity is %lld", (long long) nout,
             (long long) y_capacity);
   TSD_CHECK(nout == 0 || y != nullptr, "resampler_step: NULL output");
+  // (the cycle before the table: whichever the kernel is told, the table uploaded after it covers it)
+  const RsCycle cy = r->sch->cycle();
   int rc = sync_table(r, st);
   if (rc) return rc;
-  const size_t sz = dtype_size(r->data_type);
   const void *dx = nullptr;
   void *dy = nullptr;
   bool staged = false;
@@ -1374,94 +1265,34 @@ int tsdgpu_resampler_step(tsdgpu_resampler *r, const void *x, int64_t n, void *y
   rc = stage_out(y, (size_t) nout * sz, r->out_stage, &dy, &staged);
   if (rc) return rc;
 
-  RsParams P;
-  P.pos = r->pos;
-  P.n = n;
-  P.tile0 = (r->pos / RS_TI) * RS_TI;
-  P.mu = r->cyc ? r->mu : 0;
-  P.lambda = r->cyc ? r->lambda : 0;
-  P.opp = r->opp;
-  P.cum_pos = r->cum_pos;
-  P.inc = r->inc;
-  P.K = r->K;
-  P.nph = r->nph;
-  P.lstride = r->lstride;
-  P.mode = r->mode;
-  P.gl = r->gl;
-  for (int j = 0; j < 32; j++) P.inv_den[j] = r->inv_den[j];
-  // at most floor(1/inc)+1 outputs per input
-  // outputs are spaced 1/ratio apart in input time (up to float32 rounding of the adds)
-  P.rec_cap = ((int) ((double) RS_TI * (double) r->ratio * 1.0001) + 32 + 3) / 4 * 4;
-  const int64_t tiles = cdiv(r->pos + n - P.tile0, RS_TI);
+  const int64_t tiles = cdiv(r->pos + n - (r->pos / RS_TI) * RS_TI, RS_TI);
   TSD_CHECK(tiles <= 0x7fffffff, "resampler_step: n too large for one launch");
-  const RsGeom geo = rs_geometry(r, r->mode);
-  P.lut_in_lds = geo.lut_in_lds ? 1 : 0;
-  const size_t lds = geo.lds;
-  TSD_CHECK(lds <= RS_LDS_LIMIT, "resampler_step: configuration needs %zu bytes of LDS", lds);
-  // persistent workgroups (the LUT is staged once per workgroup): as many as stay resident
-  int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 1024)));
-  const int64_t pgrid = std::min<int64_t>(cdiv(tiles, geo.waves), (int64_t) 256 * per_cu);
-  const void *hcur = r->hist_zero ? nullptr : r->d_hist[r->cur];
-  unsigned ctr_add = 0;
-  const char *e15 = dev_switch("RS15");                     // =0: the K = 15 interpolator through the kernels of the other lengths (parity tests)
-  // K = 15 at a ratio below 2 (at most two outputs per input): the split kernel, as many waves per workgroup as its LDS allows
-  const int rec15 = ((int) ((double) RS_TI * (double) r->ratio * 1.0001) + 8 + 3) / 4 * 4;
-  const int lcap15 = (int) ((double) RS_TI * std::max(0.0, (double) r->ratio - 1.0) * 1.0001) + 8;
-  const size_t wb15s = ((size_t) (RS15_TILE_PAD + rec15) * sz + (size_t) lcap15 * 4 + RS15S_CKB + 15) / 16 * 16;
-  const size_t lut15 = (size_t) ((r->nph + 1) * 20 + 4) * 4;
-  const int nw15s = (int) std::min<size_t>(16, (RS_LDS_LIMIT - lut15 - 64) / wb15s);
-  if (r->K == 15 && r->mode == 0 && r->inc >= 0.5f && r->nph <= 511 && nw15s >= 4 && !(e15 && atoi(e15) == 0)) {
-    const int NW = nw15s;
-    P.rec_cap = rec15;
-    int64_t g15 = std::min<int64_t>(cdiv(tiles, NW), 256);
-    const char *nc_s = dev_switch("RS_DYN");
-    int NC = nc_s ? atoi(nc_s) : 16;
-    if (NC < 0 || NC > RS_MAX_CTR || !r->d_ctr || 256 % (8 * std::max(NC, 1)) != 0 || stream_is_capturing(st)) NC = 0;
-    const char *min_s = dev_switch("RS_DYN_MIN");
-    if (tiles < (int64_t) (min_s ? atoi(min_s) : 4) * 256 * NW) NC = 0;
-    RsDyn dyn = {r->d_ctr, r->ctr_base, 0u, NC};
-    if (NC > 0) {
-      g15 = 256;
-      if (NC != r->ctr_nc) {
-        TSD_HIP(hipMemsetAsync(r->d_ctr, 0, (size_t) RS_MAX_CTR * 128, st));
-        r->ctr_base = 0;
-        r->ctr_nc = NC;
-        dyn.base = 0;
-      }
-      dyn.Q = (unsigned) cdiv(tiles, NC);
-      ctr_add = dyn.Q + (unsigned) (g15 / NC * NW);
-    }
-    const size_t lds15s = lut15 + (size_t) NW * wb15s + 64;
-    if (r->data_type == TSDGPU_C64)
-      hipLaunchKernelGGL(resample15s_kernel<float2>, dim3((unsigned) g15 + 1), dim3(64 * NW), lds15s, st, (const float2 *) dx,
-                         (const float2 *) hcur, (float2 *) dy, r->d_lut, r->d_ck, r->d_ph, P, (int) tiles, (float2 *) r->d_hist[r->cur ^ 1], dyn, lcap15);
+  const RsPlan pl = rs_plan(r, tiles, st);
+  TSD_CHECK(pl.gen_lds <= RS_LDS_LIMIT, "resampler_step: configuration needs %zu bytes of LDS", pl.gen_lds);
+  const RsParams P = rs_params(r, n, cy, pl);
+  RsDyn dyn;
+  rc = r->ctr.begin(pl.NC, tiles, pl.grid, pl.waves, st, &dyn);
+  if (rc) return rc;
+  type_switch(r->data_type, [&](auto tag) {
+    using T = decltype(tag);
+    const T *tx = (const T *) dx, *th = r->hist_zero ? nullptr : (const T *) r->d_hist[r->cur];
+    T *ty = (T *) dy, *tn = (T *) r->d_hist[r->cur ^ 1];
+    const dim3 grid((unsigned) pl.grid + 1), block(64 * pl.waves);
+    if (pl.kernel == RsPlan::K15S)
+      hipLaunchKernelGGL(resample15s_kernel<T>, grid, block, pl.lds, st, tx, th, ty, r->d_lut, r->d_ck, r->d_ph, P, (int) tiles, tn, dyn, pl.lcap15);
+    else if (pl.kernel == RsPlan::LONG)
+      hipLaunchKernelGGL(resample_long_kernel<T>, grid, block, pl.lds, st, tx, th, ty, r->d_lut, r->d_ck, P, (int) tiles, tn, pl.lg.cap2, pl.lg.kp,
+                         pl.lg.nphase);
     else
-      hipLaunchKernelGGL(resample15s_kernel<float>, dim3((unsigned) g15 + 1), dim3(64 * NW), lds15s, st, (const float *) dx,
-                         (const float *) hcur, (float *) dy, r->d_lut, r->d_ck, r->d_ph, P, (int) tiles, (float *) r->d_hist[r->cur ^ 1], dyn, lcap15);
-  } else if (const RsLongGeom lg = rs_long_geometry(r); lg.waves > 0) {
-    const int64_t lgrid = std::min<int64_t>(cdiv(tiles, lg.waves), 256);
-    if (r->data_type == TSDGPU_C64)
-      hipLaunchKernelGGL(resample_long_kernel<float2>, dim3((unsigned) lgrid + 1), dim3(64 * lg.waves), lg.lds, st, (const float2 *) dx,
-                         (const float2 *) hcur, (float2 *) dy, r->d_lut, r->d_ck, P, (int) tiles, (float2 *) r->d_hist[r->cur ^ 1], lg.cap2, lg.kp, lg.nphase);
-    else
-      hipLaunchKernelGGL(resample_long_kernel<float>, dim3((unsigned) lgrid + 1), dim3(64 * lg.waves), lg.lds, st, (const float *) dx,
-                         (const float *) hcur, (float *) dy, r->d_lut, r->d_ck, P, (int) tiles, (float *) r->d_hist[r->cur ^ 1], lg.cap2, lg.kp, lg.nphase);
-  } else {
-#define RS_LAUNCH(T, KT)                                                                                            \
-  hipLaunchKernelGGL((resample_kernel<T, KT>), dim3((unsigned) pgrid + 1), dim3(64 * geo.waves), lds, st, (const T *) dx, \
-                     (const T *) hcur, (T *) dy, r->d_lut, r->d_ck, P, (int) tiles, (T *) r->d_hist[r->cur ^ 1])
-  if (r->data_type == TSDGPU_C64) RS_LAUNCH(float2, 0); else RS_LAUNCH(float, 0);
-#undef RS_LAUNCH
-  }
-  if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
-    if (ctr_add) r->ctr_nc = 0;   // (device counters and host base may have parted: the next dynamic launch zeroes them)
-    return set_err(TSDGPU_ERR_HIP, "resampler_step: launch failed: %s", hipGetErrorString(le));
-  }
-  r->ctr_base += ctr_add;
+      hipLaunchKernelGGL(resample_kernel<T>, grid, block, pl.lds, st, tx, th, ty, r->d_lut, r->d_ck, P, (int) tiles, tn);
+  });
+  const hipError_t le = hipGetLastError();
+  r->ctr.commit(le == hipSuccess);
+  if (le != hipSuccess) return set_err(TSDGPU_ERR_HIP, "resampler_step: launch failed: %s", hipGetErrorString(le));
   if (r->K > 1) r->cur ^= 1;      // (the launch wrote the next window history into the other buffer)
   r->hist_zero = false;
   r->pos += n;
-  r->cum_pos = cum_end;
+  r->cum_pos = end.cum;
   if (n_out) *n_out = nout;
   return finish_out(y, (size_t) nout * sz, dy, staged, st);
 }
@@ -1479,17 +1310,10 @@ int tsdgpu_resampler_seek(tsdgpu_resampler *r, int64_t pos, const void *hist, vo
 {
   TSD_CHECK(r != nullptr && pos >= 0, "resampler_seek: bad argument");
   hipStream_t st = (hipStream_t) stream;
-  float ph;
-  int64_t c;
-  {
-    std::lock_guard<std::mutex> lock(r->sch->mtx);
-    state_at(r, pos, &ph, &c);
-    if (r->sch->failed)
-      return set_err(TSDGPU_ERR_UNSUPPORTED, "resampler_seek: the float32 phase recurrence of ratio %g shows no period within 2^29 inputs",
-                     (double) r->ratio);
-  }
+  RsState s;
+  if (!r->sch->state_at(pos, &s)) return rs_no_period("resampler_seek", r);
   r->pos = pos;
-  r->cum_pos = c;
+  r->cum_pos = s.cum;
   if (hist && r->K > 1) {
     const size_t hb = (size_t) (r->K - 1) * dtype_size(r->data_type);
     if (is_device_ptr(hist)) {
@@ -1511,7 +1335,7 @@ int64_t tsdgpu_resampler_out_offset(const tsdgpu_resampler *r) { return r ? r->c
 int tsdgpu_resampler_destroy(tsdgpu_resampler *r)
 {
   if (!r) return TSDGPU_OK;
-  if (r->d_lut) (void) hipFree(r->d_lut);            // (the window histories live in the same allocation)
+  if (r->d_lut) (void) hipFree(r->d_lut);            // (the window histories and the counters live in the same allocation)
   if (r->d_ck) (void) hipFree(r->d_ck);
   r->in_stage.release();
   r->out_stage.release();

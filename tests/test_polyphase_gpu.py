@@ -39,6 +39,20 @@ def test_decimateur_exact(tg, orc):
     for R in (2, 5, 7):
         xx = rand(1000, True, R)
         assert np.array_equal(chunks(tg.PolyFir(tg.POLY_PICK, tg.C64, None, R), xx, 33), xx[::R])
+    # status and whole text of tsdgpu_last_error() of the refusals that need a device, as literals (the others: test_rate_refusals_cpu.py)
+    import ctypes as C
+    L = tg.lib()
+    p = tg.PolyFir(tg.POLY_DECIM, tg.F32, np.ones(15, np.float32) / 15, 2)
+    x, y = np.ones(16, np.float32), np.zeros(64, np.float32)
+    got = C.c_int64(7)
+    assert L.tsdgpu_polyfir_step(p._h, x.ctypes.data, 16, y.ctypes.data, 7, C.byref(got), None) == 1
+    assert L.tsdgpu_last_error().decode() == 'polyfir_step: output needs 8 samples, capacity is 7'
+    assert L.tsdgpu_polyfir_step(p._h, x.ctypes.data, 16, None, 64, C.byref(got), None) == 1
+    assert L.tsdgpu_last_error().decode() == 'polyfir_step: NULL buffer'
+    assert L.tsdgpu_polyfir_step(p._h, None, 16, y.ctypes.data, 64, C.byref(got), None) == 1
+    assert L.tsdgpu_last_error().decode() == 'polyfir_step: NULL buffer'
+    assert got.value == 0
+    assert len(p.step(x)) == 8                           # (nothing advanced)
 
 
 @pytest.mark.parametrize("cplx", [False, True])

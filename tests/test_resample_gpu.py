@@ -229,6 +229,31 @@ def test_resampler_create_refuses_what_no_step_can_launch(tg):
     r = tg.Resampler(5.0, tg.F32, lut=lut)          # a large ratio that does fit keeps working
     x = np.ones(1000, np.float32)
     assert abs(len(r.step(x)) - 5000) <= 2
+    # status and whole text of tsdgpu_last_error() of the refusals that need a device, as literals (the others: test_rate_refusals_cpu.py)
+    import ctypes as C
+
+    def _refused(tg, call):
+        rc = call(tg.lib())
+        return rc, tg.lib().tsdgpu_last_error().decode()
+
+    h = C.c_void_p()
+    assert _refused(tg, lambda L: L.tsdgpu_resampler_create(C.byref(h), tg.C64, 8.0, lut.ctypes.data, 15, 256)) == (
+        3, 'resampler_create: ratio 8 with 15 taps on complex data needs 187680 bytes of LDS per workgroup (limit 158 KiB): '
+           'fold the ratio with half-band stages first (filtre_reechan does)')
+    assert not h.value
+    # (the analytic interpolators keep the phase beside each output's record: the same tiles need more)
+    assert _refused(tg, lambda L: L.tsdgpu_resampler_create_analytic(C.byref(h), tg.C64, 5.0, 1, 0)) == (
+        3, 'resampler_create_analytic: ratio 5 needs more LDS than a workgroup has: fold the ratio first')
+    assert not h.value
+    r = tg.Resampler(2.0, tg.F32, lut=lut)
+    x, y = np.ones(16, np.float32), np.zeros(64, np.float32)
+    got = C.c_int64(7)
+    assert _refused(tg, lambda L: L.tsdgpu_resampler_step(r._h, x.ctypes.data, 16, y.ctypes.data, 31, C.byref(got), None)) == (
+        1, 'resampler_step: output needs 32 samples, capacity is 31')
+    assert _refused(tg, lambda L: L.tsdgpu_resampler_step(r._h, x.ctypes.data, 16, None, 64, C.byref(got), None)) == (
+        1, 'resampler_step: NULL output')
+    assert got.value == 0 and r.out_offset == 0          # (nothing advanced)
+    assert len(r.step(x)) == 32
 
 
 @pytest.mark.parametrize("ratio", [1.0, 0.5, 1.25, 1.5, 2.5])
